@@ -2,6 +2,7 @@
 """Benchmark of the captioning hot path (BASELINE.json metric: greedy captions/sec + decoder-step us).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp16|fp32|fp16x3] [--config NAME]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one full pass of the hot path over one batch of B synthetic clips per GPU:
 per-modality embedding -> (concept head) -> cross-K/V projection -> 29 greedy decoder
@@ -10,9 +11,13 @@ steps with the fused vocabulary argmax, plus the RCCL all-gather of the per-rank
 resident in HBM before the timed region.  Workload = BASELINE.json configs[1]
 (MSRVTT Transformer/base, task Base, feats ViT, modality ami, bf16 greedy, 28-frame feats).
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around every
-launch of each tagged kernel in an extra instrumented pass on the same workload;
-`cpu_baseline` times the CPU oracle (the reference algorithm as written) on the host cores.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints
+the headline (`value`, `ms_per_step`).  `--full` adds what takes runs of its own: `roofline`
+and `kernels`, measured live with HIP events around every launch of each tagged kernel in an
+extra instrumented pass on the same workload; `cpu_baseline`, the CPU oracle (the reference
+algorithm as written) timed on the host cores; and the `legs` (other configurations, sizes,
+precisions and entry points).  `--dump-outputs DIR` writes what the last timed step returned
+to its caller as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import json
@@ -45,10 +50,16 @@ def parse():
                     help="batch lanes on separate HIP streams inside the captured graph (engine.lanes_for): 2 gives "
                          "+5-8%% at B >= 4096; the default 1 keeps every kernel alone on the chip so that the "
                          "per-kernel roofline and profiles/ describe the timed pass exactly")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the instrumented per-kernel pass "
+                         "(`roofline`, `kernels`, `decoder_step_us`), the CPU baseline, the extra legs and the bare exchange "
+                         "time of N > 1; a plain run does only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the extra legs (other BASELINE configs, beam 5, fp32, B = 128, crafted-EOS early exit, "
-                         "bf16 error) that rank 0 reports in `legs` beside the headline measurement at N = 1")
+                    help="with --full: skip the extra legs (other BASELINE configs, beam 5, fp32, B = 128, crafted-EOS early "
+                         "exit, bf16 error) that rank 0 reports in `legs` beside the headline measurement at N = 1")
     ap.add_argument("--cpu-batch", type=int, default=128)
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="torch threads for the CPU oracle (16 was the fastest of 8..128 on the 2x64-core host)")
@@ -206,6 +217,30 @@ def _timed_median(fn, iters, repeats=3):
     """Median over `repeats` loops of _timed(fn, iters): for the legs that time HOST work call by call (the drop-in API), where
     one 30 ms hiccup of a shared host inside a 60 ms loop halves the figure (seen in 3 of 8 runs on the 4-tenant boxes of round 6)."""
     return sorted(_timed(fn, iters) for _ in range(repeats))[repeats // 2]
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the tensors the timed path handed its caller in the last timed step -> out_dir/<name>.npy, floating
+    ones as float32, integer ones (token ids, lengths) as float64, which holds them exactly.  Every array has one row per
+    clip; above DUMP_MAX_BYTES in all, the same fixed, seeded sample of clips is kept from each, its indices in
+    sample_rows.npy."""
+    import numpy as np
+
+    host = {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else torch.float64).numpy()
+            for k, v in arrays.items()}
+    n = next(iter(host.values())).shape[0]
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_MAX_BYTES:
+        keep = int((DUMP_MAX_BYTES - 4096) // (total / n + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {k: v[rows] for k, v in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
 
 
 def extra_legs(dev, main_dtype, legs):
@@ -728,32 +763,36 @@ def main():
     feats = [torch.randn(shape, generator=gen, device=dev, dtype=torch.float32) for shape in feat_shapes(opt, B)]
     torch.cuda.synchronize()
 
-    from care_amd.sharding import all_gather_records, pack_records
+    from care_amd.sharding import all_gather_records, pack_records, unpack_records
 
     gathered = None
     if use_dist:
         gathered = [torch.empty(B, eng.T + 4, device=dev, dtype=torch.int32) for _ in range(world)]
 
     if args.beam > 1:
-        for _ in range(3):
+        for _ in range(max(args.warmup, 2)):
             eng.translate_beam(feats, args.beam, args.beam, use_graph=not args.no_graph, lean=True)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            eng.translate_beam(feats, args.beam, args.beam, use_graph=not args.no_graph, lean=True)
+            _, nfin, fscore, flen, fhyp = eng.translate_beam(feats, args.beam, args.beam, use_graph=not args.no_graph, lean=True)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
-        _lib.TIMING = {}   # instrumented pass (untimed): HIP events around every tagged launch
-        eng.translate_beam(feats, args.beam, args.beam, use_graph=False, lean=True)
-        torch.cuda.synchronize()
-        timing, _lib.TIMING = _lib.TIMING, None
-        kernels = {t: dict(launches=len(ev), avg_us=round(1e3 * sum(s.elapsed_time(e) for s, e in ev) / len(ev), 2),
-                           total_ms=round(sum(s.elapsed_time(e) for s, e in ev), 3)) for t, ev in timing.items()}
-        kernels = dict(sorted(kernels.items(), key=lambda kv: -kv[1]["total_ms"]))
-        print(json.dumps(dict(metric="captions/sec (beam %d)" % args.beam, value=round(B / dt, 1), unit="captions/s",
-                              n_gpus=1, steps=args.steps, ms_per_step=round(dt * 1e3, 3), dtype=args.dtype, kernels=kernels,
-                              config=dict(config_name=args.config, clips_per_gpu_per_step=B, beam_size=args.beam,
-                                          rows_per_decoder_step=B * args.beam))), flush=True)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, dict(nfin=nfin, fscore=fscore, flen=flen, fhyp=fhyp))
+        line = dict(metric="captions/sec (beam %d)" % args.beam, value=round(B / dt, 1), unit="captions/s",
+                    n_gpus=1, steps=args.steps, warmup=args.warmup, ms_per_step=round(dt * 1e3, 3), higher_is_better=True,
+                    dtype=args.dtype, config=dict(config_name=args.config, clips_per_gpu_per_step=B, beam_size=args.beam,
+                                                  rows_per_decoder_step=B * args.beam))
+        if args.full:
+            _lib.TIMING = {}   # instrumented pass (untimed): HIP events around every tagged launch
+            eng.translate_beam(feats, args.beam, args.beam, use_graph=False, lean=True)
+            torch.cuda.synchronize()
+            timing, _lib.TIMING = _lib.TIMING, None
+            kernels = {t: dict(launches=len(ev), avg_us=round(1e3 * sum(s.elapsed_time(e) for s, e in ev) / len(ev), 2),
+                               total_ms=round(sum(s.elapsed_time(e) for s, e in ev), 3)) for t, ev in timing.items()}
+            line["kernels"] = dict(sorted(kernels.items(), key=lambda kv: -kv[1]["total_ms"]))
+        print(json.dumps(line), flush=True)
         return
 
     def step():
@@ -772,35 +811,37 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        fed, length, score = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    # what the last timed pass did (read after the clock stopped): decoder steps run, caption lengths - a pass that ended early
+    # or returned a previous batch's rows would be fast for the wrong reason
+    work_done = dict(decoder_steps_run=int(eng.last_decode.get("steps", eng.T)), caption_length_min=int(length.min()),
+                     caption_length_mean=round(float(length.float().mean()), 2), captions=int(length.numel()))
+    if args.dump_outputs and rank == 0:   # what the caller of the timed path holds: every rank's captions when N > 1
+        tok, ln, sc = unpack_records(torch.cat(gathered)) if use_dist else (fed, length, score)
+        dump_outputs(args.dump_outputs, dict(tokens=tok, lengths=ln, scores=sc))
     dist_info = None
     if use_dist:
         mine = torch.tensor([elapsed, float(rank)], device=dev, dtype=torch.float64)
         every = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         per_rank_s = [float(e[0]) for e in every]
-        # the exchange alone: the all-gather of one batch's records, back to back
-        rec = pack_records(*step(), B)
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(20):
-            all_gather_records(rec, gathered)
-        barrier()
         dist_info = dict(backend="nccl (RCCL)", rccl_ranks_seen=sorted(int(e[1]) for e in every),
-                         per_rank_captions_per_s=[round(B * args.steps / t, 1) for t in per_rank_s],
-                         all_gather_us=round((time.perf_counter() - t1) / 20 * 1e6, 1),
-                         all_gather_bytes_per_rank=int(rec.numel() * rec.element_size()))
+                         per_rank_captions_per_s=[round(B * args.steps / t, 1) for t in per_rank_s])
+        if args.full:
+            # the exchange alone: the all-gather of one batch's records, back to back
+            rec = pack_records(*step(), B)
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(20):
+                all_gather_records(rec, gathered)
+            barrier()
+            dist_info.update(all_gather_us=round((time.perf_counter() - t1) / 20 * 1e6, 1),
+                             all_gather_bytes_per_rank=int(rec.numel() * rec.element_size()))
         elapsed = max(per_rank_s)
     ms_per_step = elapsed / args.steps * 1e3
     value = world * B * args.steps / elapsed
-    # what the last timed pass did (after the clock stopped): decoder steps run, caption lengths - a pass that ended early or
-    # returned a previous batch's rows would be fast for the wrong reason
-    _, length_chk, _ = step()
-    torch.cuda.synchronize()
-    work_done = dict(decoder_steps_run=int(eng.last_decode.get("steps", eng.T)), caption_length_min=int(length_chk.min()),
-                     caption_length_mean=round(float(length_chk.float().mean()), 2), captions=int(length_chk.numel()))
 
     if rank != 0:
         if use_dist:
@@ -808,6 +849,35 @@ def main():
             dist.destroy_process_group()
         return
 
+    # ---- whole-pass algorithmic work (SURVEY.md 8(d)): FLOPs per caption
+    d, ff, V, Lk, T = eng.d, eng.ff, eng.V, eng.Lk, eng.T
+    enc_fl = sum(2 * eng.rows_of[ch] * d * opt["dim_" + ch] for ch in eng.modality)
+    step_fl = 2 * d * d * 6 + 4 * d * ff + 2 * d * V + 4 * Lk * d
+    total_fl = enc_fl + 4 * Lk * d * d + sum(step_fl + 4 * t * d for t in range(1, T + 1))
+    line = dict(
+        metric="captions/sec (greedy)", value=round(value, 1), unit="captions/s", n_gpus=world, steps=args.steps,
+        warmup=args.warmup, ms_per_step=round(ms_per_step, 3), higher_is_better=True, scaling="weak",
+        vs_baseline=None, dtype={"bf16": "bf16", "fp16": "f16", "fp32": "f32", "fp16x3": "f16x3"}[args.dtype], data="synthetic",
+        config=dict(workload="MSRVTT Transformer/base task=Base feats=ViT modality=ami greedy "
+                             "(BASELINE.json configs[1]): [B,28,128]+[B,28,2048]+[B,28,512] fp32 feats, d=512, "
+                             "V=10547, 29 decoder steps" if args.config == "msrvtt_base_ami" else args.config,
+                    config_name=args.config, clips_per_gpu_per_step=B, global_batch=B * world, lanes=args.lanes,
+                    parallelism="batch-sharded dp{} (no data-path collective; all-gather of results)".format(world),
+                    hip_graph=not args.no_graph, absorbed_cross_attention=bool(eng.latent_for(B)),
+                    lean_encode=bool(eng.lean_ok),  # the Translator's call: bf16 memory only, no unused fp32 copy / frame means
+                    work_done_per_step=work_done),
+        gflop_per_caption=round(total_fl / 1e9, 4),
+        pass_tflops=round(total_fl * value / 1e12, 2))
+    if dist_info:
+        line["distributed"] = dist_info
+    if not args.full:
+        print(json.dumps(line), flush=True)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on: what takes runs of its own beside the timed steps
     # ---- instrumented pass (untimed): HIP events around every tagged launch, same workload
     _lib.TIMING = {}
     eng.translate_greedy(feats, use_graph=False, lean=True)
@@ -900,12 +970,6 @@ def main():
             ent["TFLOPs"] = round(m["flops"] / (k["avg_us"] * 1e-6) / 1e12, 2)
         per_kernel[tag] = ent
 
-    # ---- whole-pass algorithmic work (SURVEY.md 8(d)): FLOPs per caption
-    d, ff, V, Lk, T = eng.d, eng.ff, eng.V, eng.Lk, eng.T
-    enc_fl = sum(2 * eng.rows_of[ch] * d * opt["dim_" + ch] for ch in eng.modality)
-    step_fl = 2 * d * d * 6 + 4 * d * ff + 2 * d * V + 4 * Lk * d
-    total_fl = enc_fl + 4 * Lk * d * d + sum(step_fl + 4 * t * d for t in range(1, T + 1))
-
     # ---- CPU baseline: the oracle (reference algorithm as written) on the host cores
     cpu = None
     if not args.no_cpu_baseline and world == 1:  # contract: rank 0 at N=1 only
@@ -927,26 +991,11 @@ def main():
                           "host)".format(passes, cb, cpu_s / T * 1e6, args.cpu_threads),
                    host_cpus=os.cpu_count())
 
-    line = dict(
-        metric="captions/sec (greedy)", value=round(value, 1), unit="captions/s", n_gpus=world, steps=args.steps,
-        warmup=args.warmup, ms_per_step=round(ms_per_step, 3), higher_is_better=True, scaling="weak",
-        vs_baseline=None, dtype={"bf16": "bf16", "fp16": "f16", "fp32": "f32", "fp16x3": "f16x3"}[args.dtype], data="synthetic",
-        config=dict(workload="MSRVTT Transformer/base task=Base feats=ViT modality=ami greedy "
-                             "(BASELINE.json configs[1]): [B,28,128]+[B,28,2048]+[B,28,512] fp32 feats, d=512, "
-                             "V=10547, 29 decoder steps" if args.config == "msrvtt_base_ami" else args.config,
-                    config_name=args.config, clips_per_gpu_per_step=B, global_batch=B * world, lanes=args.lanes,
-                    parallelism="batch-sharded dp{} (no data-path collective; all-gather of results)".format(world),
-                    hip_graph=not args.no_graph, absorbed_cross_attention=bool(eng.latent_for(B)),
-                    lean_encode=bool(eng.lean_ok),  # the Translator's call: bf16 memory only, no unused fp32 copy / frame means
-                    work_done_per_step=work_done),
+    line.update(
         decoder_step_us=round(ms_per_step * 1e3 * (1 - (kernels.get("enc_gemm", {"total_ms": 0})["total_ms"] +
                                                          kernels.get("cross_kv_gemm", {"total_ms": 0})["total_ms"]) /
                                                     max(tagged_ms, 1e-9)) / T, 2),
-        gflop_per_caption=round(total_fl / 1e9, 4),
-        pass_tflops=round(total_fl * value / 1e12, 2),
         roofline=roofline, kernels=per_kernel, cpu_baseline=cpu)
-    if dist_info:
-        line["distributed"] = dist_info
     if world == 1 and not args.no_legs and args.beam == 1:
         del model, eng, feats
         torch.cuda.empty_cache()

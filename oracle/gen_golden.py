@@ -260,6 +260,64 @@ def host_helpers_golden():
     print("host_helpers.json written")
 
 
+# Options outside the shipped configurations (tests/test_oracle_vs_reference.py; tests/test_gpu_parity.py then holds the HIP
+# path to the oracle on the same shapes): name, config, opt overrides, topk, row_scale.  Beam 5, two clips, seed 7.
+OPTION_BOOST = {VOCAB_W: {EOS_ROW: 4.0, PAD_ROW: 3.0}}
+OPTION_VARIANTS = [(name, cfg, over, 2, OPTION_BOOST) for name, cfg, over in [
+    ("frames8", "msrvtt_care", dict(n_frames=8)),
+    ("vocab2003", "msrvtt_care", dict(vocab_size=2003)),
+    ("alpha07", "msrvtt_care", dict(beam_alpha=0.7)),
+    ("topk12_k300", "msrvtt_care", dict(use_attr_topk=12, attribute_prediction_k=300)),
+    ("d256", "msrvtt_base_ami", dict(dim_hidden=256, num_attention_heads=4, intermediate_size=1024)),
+    ("layers2", "msrvtt_care", dict(num_hidden_layers_decoder=2)),
+    ("max_len12", "msrvtt_care", dict(max_len=12)),
+    ("max_len45", "msrvtt_base_ami", dict(max_len=45)),
+    ("sinusoid_pe", "msrvtt_care", dict(trainable_pe=False)),
+    ("no_qkv_bias", "msrvtt_base_ami", dict(mha_exclude_bias=True)),
+    ("no_hybrid_bias", "msrvtt_care", dict(add_hybrid_attention_bias=False)),
+    ("decoder_mi", "msrvtt_base_ami", dict(modality_for_decoder="mi")),
+    ("predictor_mi", "msrvtt_care", dict(modality_for_predictor="mi")),
+    ("eps1e-6", "msrvtt_base_ami", dict(layer_norm_eps=1e-6)),
+    ("modality_ai", "msrvtt_base_ami", dict(modality="ai")),
+    ("share_prj", "msrvtt_care", dict(attribute_prediction_share_prj=True)),
+    ("retrieval10", "msrvtt_care", dict(retrieval_topk=10)),
+    ("dims_64_1024_768", "msrvtt_base_ami", dict(dim_a=64, dim_m=1024, dim_i=768)),
+    ("dim_i_500", "msvd_base_i", dict(dim_i=500)),
+    ("vocab100", "msrvtt_base_ami", dict(vocab_size=100)),
+    ("d192", "msrvtt_care", dict(dim_hidden=192, num_attention_heads=3, intermediate_size=768)),
+    ("d320_ff1280", "msrvtt_base_ami", dict(dim_hidden=320, num_attention_heads=5, intermediate_size=1280)),
+]]
+# `use_attr_flags` Gp..: the guidance vector prepended to the decoder's input - a layout the oracle does not restate
+PREFIX_GUIDANCE = ("prefix_guidance", "msrvtt_care", dict(use_attr_type="pp_emb_concat"), 1, {})
+
+
+def option_variants_golden(get_framework, get_translator):
+    """The reference's beam-5 captions and scores, and its parameter names and shapes, per option variant ->
+    option_variants.json; the inputs are regenerated from the seed, their hashes stored."""
+    seed, B, beam = 7, 2, 5
+    out = {}
+    for name, cfg, over, topk, row_scale in OPTION_VARIANTS + [PREFIX_GUIDANCE]:
+        opt = make_opt(cfg, beam_size=beam, topk=topk, **over)
+        torch.manual_seed(0)
+        ref = get_framework(opt).eval()
+        shapes = [(k, tuple(v.shape)) for k, v in ref.state_dict().items()]
+        sd = synth_state_dict(seed, shapes, row_scale=row_scale)
+        ref.load_state_dict(sd, strict=True)
+        feats = synth_feats(seed, feat_shapes(opt, B))
+        with torch.no_grad():
+            hyps, scores = get_translator(opt).translate_batch([ref], {"feats": [f.clone() for f in feats]})
+        out[name] = dict(config=cfg, overrides=over, beam_size=beam, topk=topk, seed=seed, batch=B,
+                         row_scale={k: {str(r): f for r, f in v.items()} for k, v in row_scale.items()},
+                         state_dict=[[k, list(s)] for k, s in shapes],
+                         sha256=dict(feats0=tensor_sha256(feats[0]), **{VOCAB_W: tensor_sha256(sd[VOCAB_W])}),
+                         hyps=[[[int(t) for t in h] for h in hs] for hs in hyps],
+                         scores=[[float(s) for s in ss] for ss in scores])
+    with open(os.path.join(OUT_DIR, "option_variants.json"), "w") as fh:
+        json.dump(dict(generator_version=GENERATOR_VERSION, cases=out), fh, separators=(",", ":"))
+        fh.write("\n")
+    print("option_variants.json written ({} cases)".format(len(out)))
+
+
 def search_peaked(cfg, B, first, last):
     """Seed search for the peaked cases (oracle only; the chosen seed is then run through the reference)."""
     from care_amd import get_framework as build_framework
@@ -288,6 +346,8 @@ def main():
     only = set(sys.argv[1:])
     if not only or "host_helpers" in only:
         host_helpers_golden()
+    if not only or "option_variants" in only:
+        option_variants_golden(get_framework, get_translator)
     for case in CASES:
         if only and case[0] not in only:
             continue

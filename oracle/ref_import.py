@@ -1,7 +1,7 @@
 """Import the genuine reference (read-only, /root/reference) in the build container.
 
-Only used by `gen_golden.py` and by the optional `tests/test_oracle_vs_reference.py`
-(skipped when /root/reference is absent, e.g. on the GPU box).  Two third-party
+Only used by `gen_golden.py`, which records the reference's outputs as the fixtures of
+`tests/golden/`; no test imports the reference.  Two third-party
 packages the reference imports eagerly are absent from this image and irrelevant to
 the forward path; they are replaced by empty stand-in *modules* (not reference code):
 `pytorch_lightning` (models/__init__.py:1 -> Wrapper.py) and `pycocoevalcap`

@@ -177,3 +177,32 @@ def test_bench_refuses_more_gpus_than_the_host_has():
     out = _bench("--gpus", str(want), "--steps", "1", timeout=120)
     assert out.returncode != 0
     assert "--gpus {}".format(want) in out.stderr and "visible" in out.stderr
+
+
+def test_bench_dump_outputs_are_float_arrays_within_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: integer outputs as float64 (exact), floating ones as float32; above the cap ONE fixed, seeded
+    sample of clips - the same rows of every array, from run to run - with its indices beside them."""
+    import numpy as np
+
+    import bench
+
+    gen = torch.Generator().manual_seed(0)
+    tok = torch.randint(0, 10547, (3000, 30), generator=gen, dtype=torch.int32)
+    ln = torch.randint(1, 30, (3000,), generator=gen, dtype=torch.int32)
+    sc = torch.randn(3000, generator=gen).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "all"), dict(tokens=tok, lengths=ln, scores=sc))
+    assert sorted(f.name for f in (tmp_path / "all").iterdir()) == ["lengths.npy", "scores.npy", "tokens.npy"]
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("tokens", "lengths", "scores")}
+    assert got["tokens"].dtype == got["lengths"].dtype == np.float64 and got["scores"].dtype == np.float32
+    assert np.array_equal(got["tokens"], tok.numpy()) and np.array_equal(got["lengths"], ln.numpy())
+    assert np.array_equal(got["scores"], sc.float().numpy())
+
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 200_000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), dict(tokens=tok, lengths=ln, scores=sc))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 200_000
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy")) and len(set(rows.tolist())) == len(rows) > 100
+    rows = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "tokens.npy"), tok.numpy()[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "lengths.npy"), ln.numpy()[rows])

@@ -508,13 +508,43 @@ def test_bench_under_torchrun_with_rccl():
     env = dict(os.environ, CARE_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2",
-           "--warmup", "2", "--batch", "256", "--no-cpu-baseline", "--no-legs"]
+           "--warmup", "2", "--batch", "256", "--full", "--no-cpu-baseline", "--no-legs"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["roofline"]["frac"] > 0
     d = line["distributed"]  # the N > 1 report: who took part, what each rank did, what the exchange costs
     assert d["rccl_ranks_seen"] == [0] and d["per_rank_captions_per_s"][0] > 0 and d["all_gather_us"] > 0
+
+
+def test_bench_plain_run_reports_the_headline_and_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the headline and nothing that takes runs of its own; --dump-outputs writes the last timed
+    step's token ids, lengths and scores (the step `work_done_per_step` describes), the same from run to run."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "256",
+               "--dump-outputs", str(tmp_path / d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "captions/s" and line["dtype"] == "bf16"
+    assert not {"roofline", "kernels", "decoder_step_us", "cpu_baseline", "legs"} & set(line)
+    got = [{n: np.load(tmp_path / d / (n + ".npy")) for n in ("tokens", "lengths", "scores")} for d in ("a", "b")]
+    tok, ln, sc = got[0]["tokens"], got[0]["lengths"], got[0]["scores"]
+    assert tok.shape == (256, 30) and ln.shape == sc.shape == (256,)
+    assert tok.dtype == ln.dtype == np.float64 and sc.dtype == np.float32
+    work = line["config"]["work_done_per_step"]
+    assert work["captions"] == 256 and work["caption_length_min"] == ln.min()
+    for n in ("tokens", "lengths", "scores"):
+        assert np.array_equal(got[0][n], got[1][n]), n
 
 
 @pytest.mark.parametrize("mode", H16)

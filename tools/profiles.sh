@@ -4,7 +4,7 @@
 # Counters are collected in passes of their own (kernel-trace only beside --pmc).
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; ROUND=${ROUND:-r06}; O=$R/gpurun_out/${ROUND}prof; mkdir -p $O
-B="python3 $R/bench.py --no-cpu-baseline --no-legs"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-legs"
 stats() {  # name, command...: kernel trace with --stats, keeps the summary csv
   local name=$1; shift
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/$name -o t -- "$@" > $O/$name.log 2>&1
@@ -44,8 +44,8 @@ PY
 pmc fetch FETCH_SIZE $B --steps 1 --warmup 2 --no-graph
 pmc write WRITE_SIZE $B --steps 1 --warmup 2 --no-graph
 pmc sq "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" python3 $R/tools/pmc_target.py 32768
-pmc sq_resident "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_IFETCH" python3 $R/bench.py --no-cpu-baseline --no-legs --batch 128 --beam 5 --config msrvtt_care_beam5 --steps 3 --warmup 2 --no-graph
-pmc icache_resident "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" python3 $R/bench.py --no-cpu-baseline --no-legs --batch 128 --beam 5 --config msrvtt_care_beam5 --steps 3 --warmup 2 --no-graph
+pmc sq_resident "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_IFETCH" python3 $R/bench.py --full --no-cpu-baseline --no-legs --batch 128 --beam 5 --config msrvtt_care_beam5 --steps 3 --warmup 2 --no-graph
+pmc icache_resident "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE" python3 $R/bench.py --full --no-cpu-baseline --no-legs --batch 128 --beam 5 --config msrvtt_care_beam5 --steps 3 --warmup 2 --no-graph
 # the phases of the resident beam launch ONE KERNEL EACH (the chained step, csrc/decode_chain.hip): counters per phase
 pmc2() {  # name, counters, command...: aggregated per kernel by tools/pmc_agg.py
   local name=$1 ctr=$2; shift 2

@@ -57,7 +57,7 @@ def copy_in():
                 out.write(open(f).read())
     fetch, write = counters("fetch"), counters("write")
     if fetch or write:
-        pm = {"command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --no-cpu-baseline --no-legs --steps 1 --warmup 2 "
+        pm = {"command": "rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python3 bench.py --full --no-cpu-baseline --no-legs --steps 1 --warmup 2 "
                          "--no-graph; a second pass with --pmc WRITE_SIZE (tools/profiles.sh)",
               "build": head,
               "note": "average per launch, KB as rocprofv3 reports them; hbm_bytes = 2 x FETCH_SIZE (gfx950 tallies wide 16-B/lane "
@@ -80,9 +80,9 @@ def copy_in():
         json.dump(tj, open(tj_path, "w"), indent=1)
     for tag, fname, cmd in (("sq", "_sq_counters.json", "python3 tools/pmc_target.py 32768"),
                             ("sq_resident", "_sq_counters_resident_beam5_B128.json",
-                             "python3 bench.py --batch 128 --beam 5 --config msrvtt_care_beam5 --no-graph"),
+                             "python3 bench.py --full --batch 128 --beam 5 --config msrvtt_care_beam5 --no-graph"),
                             ("icache_resident", "_icache_resident_beam5_B128.json",
-                             "python3 bench.py --batch 128 --beam 5 --config msrvtt_care_beam5 --no-graph")):
+                             "python3 bench.py --full --batch 128 --beam 5 --config msrvtt_care_beam5 --no-graph")):
         sq = counters(tag)
         if not sq:
             continue
@@ -122,7 +122,7 @@ def readings():
     rows = kernel_stats("bench_B32768_bf16")
     if rows:
         tot = sum(float(r["TotalDurationNs"]) for r in rows)
-        L += ["`{}_bench_B32768_bf16_kernel_stats.csv` (`rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-legs "
+        L += ["`{}_bench_B32768_bf16_kernel_stats.csv` (`rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-legs "
               "--steps 5 --warmup 2`), our kernels by total time:".format(ROUND), "", "| kernel | calls | average us | share |", "|---|---|---|---|"]
         for r in rows[:14]:
             L.append("| `{}` | {} | {:.1f} | {:.1f} % |".format(short(r["Name"]), r["Calls"], float(r["AverageNs"]) / 1e3,
