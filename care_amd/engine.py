@@ -26,7 +26,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, forms
 from ._lib import ACT_CODES, CARE_BF16, CARE_F32, ptr
 from .constants import BOS, EOS, PAD
 from .engine_beam import BeamMixin
@@ -119,32 +119,45 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
         # one pass at a time per engine: its workspaces, result block and graphs are the engine's, not the caller's - threads
         # that share a module take turns (the Translator and the module API hold it for the length of a call)
         self.lock = threading.RLock()
-        # rows (clips x beam) the running pass STARTED with: what the row-count switches of a decode step look at
-        # (ln_fusable) - compaction shrinks the row count mid-pass, and a clip's arithmetic must not change with it
-        self._form_rows: Optional[int] = None
-        # byte budget of the cached workspaces (None: 60 % of the device's memory, CARE_WS_BUDGET_GB overrides)
-        self.ws_budget_bytes: Optional[int] = None
+        # what the running (or the last) pass decided from the shape it STARTED with (care_amd/forms.py; _begin_pass): what
+        # the step code looks at - compaction shrinks the row count mid-pass, and a clip's arithmetic must not change with it.
+        # None before the first pass: a step helper called on its own chooses by the row count it is given.
+        self.plan: Optional[forms.PassPlan] = None
+        self.last_decode: dict = {}              # what the last decode actually ran (tests, bench)
+        self._cus: Optional[int] = None          # compute units of the device (load_weights)
+        self._resident_refused: Dict[str, int] = {}   # smallest row count at which a resident launch was refused (forms.resident_fits)
+        self._epoch = 0                          # (graphs of OTHER engines that stepped this one as an ensemble member: their keys carry it)
+        self._lane_streams: list = []
         self._graphs: "collections.OrderedDict[tuple, object]" = collections.OrderedDict()
         self._lane = 0
         self.lanes = 1  # batch lanes of a graph-replayed greedy pass (lanes_for)
-        self.latent = os.environ.get("CARE_LATENT", "1") != "0"
         self._ws_cap = None
-        # early termination + active-set compaction of the greedy loop (greedy_early_exit); the fixed
-        # 29-step pass remains available (`early_exit=False`, CARE_EARLY_EXIT=0)
-        self.early_exit = os.environ.get("CARE_EARLY_EXIT", "1") != "0"
-        self.segment_steps = int(os.environ.get("CARE_SEGMENT_STEPS", "4"))
+        # The environment, read HERE and nowhere else in the engine (two more are read per call because a live process
+        # toggles them: CARE_TF_OVERLAP in metrics_step, CARE_CHAIN_FORM in beam_chain_steps):
+        #   CARE_LATENT            (1)    0: projected cross K/V at every size (`latent`)
+        #   CARE_RESIDENT_MAX_ROWS (256)  `resident_max_rows`
+        #   CARE_WS_BUDGET_GB      (none) `ws_budget_bytes`: byte budget of the cached workspaces; without it 60 % of the
+        #                                 device's memory, found at the first pass
+        # Every other limit is a plain attribute: set it on the engine to force a form (forms.plan reads them per pass).
+        self.latent = os.environ.get("CARE_LATENT", "1") != "0"
         # greedy batches of up to this many clips decode as ONE resident launch (greedy_resident); 0 turns it off
         self.resident_max_rows = int(os.environ.get("CARE_RESIDENT_MAX_ROWS", "256"))
+        env = os.environ.get("CARE_WS_BUDGET_GB")
+        self.ws_budget_bytes: Optional[int] = int(float(env) * (1 << 30)) if env else None
+        # early termination + active-set compaction of the greedy loop (greedy_early_exit); the fixed
+        # 29-step pass remains available (`early_exit=False`)
+        self.early_exit = True
+        self.segment_steps = 4
         # beam search as one resident launch (csrc/decode_resident_beam.hip) up to this many rows = clips x beam_size
         # (translate.py's default: 128 clips x beam 5); 0: the multi-launch search at every size
-        self.resident_beam_max_rows = int(os.environ.get("CARE_RESIDENT_BEAM_MAX_ROWS", "640"))
+        self.resident_beam_max_rows = 640
         # ... or as a CHAIN of kernels per step (csrc/decode_chain.hip: the resident launch's phases as launches of their
         # own, bit-identical results, no residency condition) up to this many rows.  OFF by default (0): *measured*
         # (tools/beam_sweep.py, profiles/r05_beam_sweep.txt) the chain is slower than the resident launch wherever that
         # applies (640 rows: 207 against 173 us per step) and slower than the multi-launch search beyond (1280 rows:
         # 370 against 282) - DESIGN.md 4.2f says where its time goes
-        self.chain_beam_max_rows = int(os.environ.get("CARE_CHAIN_BEAM_MAX_ROWS", "0"))
-        self.chain_segment_steps = int(os.environ.get("CARE_CHAIN_SEGMENT_STEPS", "8"))
+        self.chain_beam_max_rows = 0
+        self.chain_segment_steps = 8
 
     def _code(self, t: Optional[torch.Tensor]) -> int:
         """dtype code of a tensor argument (include/care_hip.h): CARE_F32, or the library's ONE 16-bit code for a tensor
@@ -168,6 +181,7 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
         if not torch.cuda.is_available():
             raise _lib.CareHipError("no HIP device: the captioning path has no CPU fallback")
         self.device = torch.device(device)
+        self._cus = device_props(self.device).multi_processor_count
         f32 = lambda t: t.detach().to(self.device, torch.float32).contiguous()
         wt = lambda t: t.detach().to(self.device, torch.float32).to(self.wt).contiguous()
         w = {}
@@ -177,7 +191,7 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
         # So with a concept head the feature-embedding GEMMs keep fp32 operands even in bf16 mode:
         # as three fp16 MFMA passes over hi/lo pieces (care_gemm_ln_split: fp32-grade, memory within
         # ~5e-6 of the reference) where the fused kernel applies, in exact f32 MFMA
-        # otherwise (or with CARE_ENC_SPLIT=0); everything downstream of the choice is bf16.
+        # otherwise; everything downstream of the choice is bf16.
         enc_wt = f32 if (self.has_concepts and opt["encoder"] == "Embedder") else wt
         for ch in self.modality:
             p = "encoder.Encoder_{}".format(ch.upper())
@@ -250,11 +264,11 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
                     self.call("care_pack_ln_weight", ptr(W), ptr(Wp), 512, W.shape[1])
                     w[name + "#packed"] = Wp
                 elif (W is not None and name.startswith("enc_w_") and W.dtype == torch.float32 and W.shape[0] == 512 and
-                      W.shape[1] % 64 == 0 and opt["encoder"] == "Embedder" and os.environ.get("CARE_ENC_SPLIT", "1") != "0"):
+                      W.shape[1] % 64 == 0 and opt["encoder"] == "Embedder"):
                     Ws = torch.empty(3 * W.shape[1] * 512, device=self.device, dtype=self.h16)
                     self.call("care_pack_ln_weight_split", ptr(W), ptr(Ws), 512, W.shape[1])
                     w[name + "#split"] = Ws
-        if self.bf and self.has_concepts and opt["encoder"] == "Embedder" and os.environ.get("CARE_ENC_SPLIT", "1") != "0":
+        if self.bf and self.has_concepts and opt["encoder"] == "Embedder":
             # concept models the fused kernel does not cover (d_model != 512): the embedder GEMM with split products
             # through the generic kernel (care_gemm_split3) instead of its exact-f32 MFMA
             for ch in self.modality:
@@ -274,7 +288,7 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
                     self._w3[W.data_ptr()] = W3
         self.w = w
         self._graphs.clear()
-        self._epoch = getattr(self, "_epoch", 0) + 1   # (graphs of OTHER engines that stepped this one as an ensemble member: their keys carry it)
+        self._epoch += 1
 
     def _pack_attn(self, w, sd, p, name, self_attn, wt, f32):
         wq, wk, wv = (sd[p + ".SDPA.{}.weight".format(n)] for n in ("query", "key", "value"))
@@ -393,21 +407,18 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
         for k in same[: max(0, len(same) - cap)]:
             del self._graphs[k]
 
-    def _begin_pass(self):
-        """Top of every public pass (never inside one): count it, and when the cached workspaces exceed their byte
-        budget drop the least recently used ones - all but those of the previous pass, so a loop over one batch shape
-        stays warm.  Captured graphs hold raw workspace addresses, so every graph goes with them (the next passes
-        run eagerly once and re-capture)."""
+    def _begin_pass(self, plan: forms.PassPlan) -> forms.PassPlan:
+        """Top of every public pass (never inside one), with the pass's plan (plan_for): count it, and when the cached
+        workspaces exceed their byte budget drop the least recently used ones - all but those of the previous pass, so a
+        loop over one batch shape stays warm.  Captured graphs hold raw workspace addresses, so every graph goes with them
+        (the next passes run eagerly once and re-capture)."""
         self._gen += 1
-        self._form_rows = None
-        self._small_pass = False
+        self.plan = plan
         budget = self.ws_budget_bytes
         if budget is None:
-            env = os.environ.get("CARE_WS_BUDGET_GB")
-            budget = int(float(env) * (1 << 30)) if env else int(0.6 * device_props(self.device).total_memory)
-            self.ws_budget_bytes = budget
+            budget = self.ws_budget_bytes = int(0.6 * device_props(self.device).total_memory)
         if self._ws_bytes <= budget:
-            return
+            return plan
         for key in sorted(self._ws, key=lambda k: self._ws_used.get(k, 0)):
             if self._ws_bytes <= budget // 2 or self._ws_used.get(key, 0) >= self._gen - 1:
                 break
@@ -415,34 +426,55 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
             self._ws_used.pop(key, None)
             self._ws_bytes -= t.numel() * t.element_size()
         self._graphs.clear()
-        self._epoch = getattr(self, "_epoch", 0) + 1   # (graphs of OTHER engines that stepped this one as an ensemble member: their keys carry it)
+        self._epoch += 1
+        return plan
 
-    @property
+    # ------------------------------------------------------------------ forms: views of care_amd/forms.py
+    # (what tests, tools, bench.py and the entry point ask; a pass itself reads `self.plan`)
+    MID_TILE_ROWS, VOCAB_TILE_MAX_ROWS = forms.MID_TILE_ROWS, forms.VOCAB_TILE_MAX_ROWS
+    # the two thresholds that tests set on an engine to force a form at a small size
+    BEAM_FUSED_MIN_ROWS, LATENT_MIN_ROWS = forms.BEAM_FUSED_MIN_ROWS, forms.LATENT_MIN_ROWS
+
+    # (a function of forms taken as a method: the engine is its `m`)
+    plan_for = forms.plan
+    resident_ok, resident_beam_ok, chain_beam_ok = forms.resident_greedy, forms.resident_beam, forms.chain_beam
+    small_forms, ln_fusable, tf_fast_ok, lanes_for = forms.small_forms, forms.fuse_ln, forms.tf_fast, forms.lanes
+    beam_fused_for, beam_groups_for = forms.beam_fused, forms.beam_groups
+
+    def latent_for(self, rows: int) -> bool:
+        """forms.latent - except after (or inside) a beam search over a small batch, which ran on projected K/V."""
+        return forms.latent(self, rows) and not (self.plan is not None and self.plan.small_beam)
+
+    def _vocab_as(self, rows: int) -> bool:
+        """In a pass: by its INITIAL row count, like every form - compaction must not move a clip from one kernel's
+        summation order to the other's mid-pass.  Outside one (a kernel test): by the rows given."""
+        return self.plan.vocab_as if self.plan is not None else forms.vocab_as(self, rows)
+
+    # (the compute mode's flags are fixed with the model and the dtype: computed once - forms.plan reads them at every pass)
+    @functools.cached_property
     def bf(self) -> bool:
         return self.dtype in ("bf16", "fp16")
 
-    @property
+    @functools.cached_property
     def as_ok(self) -> bool:
         """bf16 mode AND d_model fits the A-stationary kernel (K = d <= 512, d % 128 == 0):
         GEMM-input activations then live as bf16 mirrors.  Otherwise (fp32 mode, d = 768/1024)
         every GEMM takes fp32 activations through the generic kernel."""
         return self.bf and self.d <= 512 and self.d % 128 == 0
 
-    @property
+    @functools.cached_property
     def bf_act(self) -> bool:
         """bf16 mode with bf16 MIRRORS of the GEMM-input activations (any d_model % 64 == 0): K = d <= 512 goes to
         the A-stationary kernels (as_ok), larger K (d_model 768 / 1024, their FFNs) to the LDS-tiled bf16 kernel
         (csrc/gemm_tile.hip)."""
         return self.bf and self.d % 64 == 0 and self.ff % 64 == 0
 
-    @property
+    @functools.cached_property
     def latent_capable(self) -> bool:
         """Shapes / dtype the absorbed cross-attention kernels cover: bf16 mode, head dim 64, d_model = 512 (one wave
         per row; per-head projections in csrc/heads.hip), 1024 (two waves per row of 512 dims each) or 768 (three waves
         of 256; per-head projections of both as one batched launch of the LDS-tiled GEMM)."""
         if self.H * 64 != self.d or self.H > 16:
-            return False
-        if os.environ.get("CARE_LATENT_WIDE", "1") == "0" and self.d != 512:
             return False
         return (self.as_ok and self.d == 512) or (self.bf_act and self.d in (768, 1024))
 
@@ -461,16 +493,6 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
         """bf16 mirror workspace of a GEMM-input activation (None unless as_ok)."""
         return self.ws(name + "#bf", shape, self.h16) if self.bf_act else None
 
-    # *measured* (round 5, tools/greedy_sweep.py / beam_sweep.py with CARE_FORCE_TILE = 0 / 1, us per decoder step of the whole
-    # pass): greedy 512 clips 137 / 141, 1024 166 / 167, 2048 248 / 232, 4096 365 / 339, 8192 590 / 568; beam 5 over 256
-    # clips (1280 rows) 284 / 272, 512 357 / 315, 1024 528 / 496, 2048 (10240 rows) 732 / 700; at 20480 rows the pass does
-    # not move and at 32768 the A-stationary kernels win in situ (DESIGN.md 10d)
-    MID_TILE_ROWS = (1280, 16384)
-    # small batches (the resident decodes): frame rows from which the embedder runs as the fused loader-wave kernel instead
-    # of GEMM + LayerNorm launches side by side (*measured* whole pass, fused / unfused: 64 clips 1.709 / 1.652 ms, 128 clips 1.809 /
-    # 1.803, 256 clips 2.637 / 2.689: from 192 clips; CARE_FUSED_SMALL_MIN_ROWS overrides)
-    FUSED_SMALL_MIN_ROWS = int(os.environ.get("CARE_FUSED_SMALL_MIN_ROWS", "5376"))
-
     def gemm(self, A, W, bias, out, act=0, out2=None, n_split=None, tag=None, tile=False):
         """out = act(A @ W^T + bias).  bf16 weights + bf16 A -> A-stationary kernel (csrc/gemm_as.hip) for
         K <= 512, the LDS-tiled bf16 kernel (csrc/gemm_tile.hip) for larger K; anything else -> the generic
@@ -484,12 +506,8 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
             if K % 64 or A.stride(0) % 8:
                 raise ValueError("bf16 A operand needs K % 64 == 0 and a 16-byte aligned row stride (got K = {})".format(K))
             # K <= 512: the A-stationary kernel (a 128-row panel's activations in registers for the whole K) - except
-            # between MID_TILE_ROWS rows, where its 128 / 256-row panels leave most of the chip idle and the LDS-tiled
-            # kernel's 128 x 128 tiles do not.  The two kernels add K in the same order: BIT-IDENTICAL outputs
-            # (tests/test_gpu_kernels.py::test_tile_and_a_stationary_gemm_agree_bit_for_bit), so the switch is by the
-            # CURRENT row count and changes no caption.
-            mid = self.MID_TILE_ROWS[0] <= M < self.MID_TILE_ROWS[1] and os.environ.get("CARE_FORCE_TILE", "") != "0"
-            if K <= 512 and K % 128 == 0 and not tile and not mid and os.environ.get("CARE_FORCE_TILE", "0") != "1":
+            # between MID_TILE_ROWS rows (forms.mid_tile: bit-identical kernels, so by the CURRENT row count)
+            if K <= 512 and K % 128 == 0 and not tile and not forms.mid_tile(M):
                 self.call("care_gemm_bf16", ptr(A), A.stride(0), self._code(A), ptr(W), *tail, tag=tag)
             else:
                 self.call("care_gemm_tile", ptr(A), A.stride(0), ptr(W), *tail, tag=tag)
@@ -504,16 +522,6 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
             else:
                 self.call("care_gemm", ptr(A), A.stride(0), ptr(W), self._code(W), *tail, tag=tag)
         return out
-
-    # up to this many rows the vocabulary arg-max of a d_model <= 512 model runs on the LDS-tiled kernel too (measured crossover
-    # between 2048 and 4096 rows on msrvtt_base_ami: 2048 rows 246 -> 241 us / step, 4096 rows 346 -> 356)
-    VOCAB_TILE_MAX_ROWS = int(os.environ.get("CARE_VOCAB_TILE_MAX_ROWS", "2048"))
-
-    def _vocab_as(self, rows: int) -> bool:
-        """The A-stationary vocabulary kernel (against the LDS-tiled one)?  Decided by the pass's INITIAL row count
-        (`_form_rows`), like ln_fusable: compaction must not move a clip from one kernel's summation order to the
-        other's mid-pass."""
-        return self.as_ok and (self._form_rows or rows) > self.VOCAB_TILE_MAX_ROWS
 
     def vocab_parts(self, rows: int) -> int:
         """Column groups per row of the fused vocabulary arg-max for `rows` rows (the kernel vocab_argmax picks)."""
@@ -555,18 +563,6 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
              nslab, x.stride(0) if nslab > 1 else 0, tag=tag)
         return out
 
-    # Unfused FFN2 (K = ff) from this many rows on the LDS-tiled kernel (one product over the whole K, no slabs) instead of
-    # the split-K slabs of the A-stationary kernel
-    FFN2_TILE_MIN_ROWS = 1 << 30
-
-    def ln_fusable(self, rows: int) -> bool:
-        """Whether dense -> (+res) -> LayerNorm runs as ONE kernel (csrc/gemm_ln.hip): bf16 mode,
-        d_model = 512, and enough 64-row panels to occupy the chip (below ~10 K rows the A-stationary
-        GEMM + LayerNorm kernel pair is faster)."""
-        # *measured* (Base `ami`, whole pass): 8192 rows 435 K captions/s unfused vs 420 K fused, 12288 rows
-        # 440 K vs 446-451 K
-        return self.as_ok and self.d == 512 and not self.pre_ln and rows >= int(os.environ.get("CARE_LN_MIN_ROWS", "10240"))
-
     # -- the two halves of a sub-block's LayerNorm placement (post-LN: after the residual sum; pre-LN: in front of the block)
     def _ln_in(self, x, xb, g, be, tag):
         """The sub-block's input: x itself (post-LN), or LayerNorm(x) (pre-LN, SubLayers.py:55,140) with its 16-bit mirror."""
@@ -588,7 +584,7 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
         rows, K = A.shape
         grp = rows if grp is None else grp
         out_grp_rows = grp if out_grp_rows is None else out_grp_rows
-        if Wp is not None and pos is None and os.environ.get("CARE_LN_PACKED", "1") != "0":
+        if Wp is not None and pos is None:
             self.call("care_gemm_ln_packed", ptr(A), A.stride(0), self._code(A), ptr(Wp), ptr(bias), ptr(res),
                  res.stride(0) if res is not None else 0, ptr(g), ptr(be), self.eps, ptr(out), ptr(outb),
                  (out if out is not None else outb).stride(-2), rows, self.d, K, grp, out_grp_rows, out_row_off, tag=tag)

@@ -7,7 +7,7 @@ from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, forms
 from ._lib import ACT_CODES, CARE_BF16, CARE_F32, ptr
 from .constants import BOS, EOS, PAD
 from .engine_util import _LaneOutputs
@@ -52,7 +52,7 @@ class DecodeMixin:
             # dense2 + bias + residual + LayerNorm in one kernel: no split-K slabs at all
             return self.gemm_ln(h, w2, w[name + "_b2"], x, w[name + "_g"], w[name + "_be"], out, outb,
                                 tag=(gemm_tag + "_ln") if gemm_tag else None, Wp=w.get(name + "_w2#packed"), **ln_kw)
-        if split and rows < int(os.environ.get("CARE_FFN2_TILE_ROWS", str(self.FFN2_TILE_MIN_ROWS))):
+        if split and rows < forms.FFN2_TILE_MIN_ROWS:
             # K = ff > 512: split K over blocks into fp32 slabs; the LayerNorm kernel sums them
             ns = self.ff // 512
             f = self.ws(tag + "fslab", (ns, rows, d))
@@ -81,17 +81,11 @@ class DecodeMixin:
         return y, yb
 
     # ------------------------------------------------------------------ teacher-forced decoder
-    def tf_fast_ok(self, t: int, want_aux: bool) -> bool:
-        """Teacher-forced forward on the fast kernels (_decode_full_fast): bf16 mode, d_model = 512, no auxiliary
-        dict entries (attention probabilities etc. are not materialised by the fused kernels)."""
-        return (self.as_ok and self.d == 512 and not want_aux and t <= 32 and not self.pre_ln and
-                os.environ.get("CARE_TF_FAST", "1") != "0")
-
     def _dense_ln(self, ctx, name, res, out, outb, rows, tag):
         """dense -> (+ residual) -> LayerNorm of an attention block (SubLayers.py:69-79): one fused kernel from
-        ~10 K rows (ln_fusable), the A-stationary GEMM + LayerNorm pair below."""
+        ~10 K rows (forms.fuse_ln), the A-stationary GEMM + LayerNorm pair below."""
         w = self.w
-        if self.ln_fusable(rows):
+        if self.plan.fuse_ln:
             return self.gemm_ln(ctx, w[name + "_o_w"], w[name + "_o_b"], res, w[name + "_g"], w[name + "_be"], out, outb,
                                 tag=tag + "_ln", Wp=w.get(name + "_o_w#packed"))
         o = self.gemm(ctx, w[name + "_o_w"], w[name + "_o_b"], self.ws("tf_o", (rows, self.d)), tag=tag + "_gemm")
@@ -137,11 +131,11 @@ class DecodeMixin:
                 x2, x2b = y, yb
             last = li == self.n_layers - 1
             xb = self.wsb("tf_x3", (rows, d))
-            if last and not hidden_fp32 and self.ln_fusable(rows) and self.ff % 512 == 0 and self.ff >= 1024:
+            if last and not hidden_fp32 and self.plan.fuse_ln and self.ff % 512 == 0 and self.ff >= 1024:
                 x = None  # scoring only reads the bf16 mirror
             else:
                 x = torch.empty(rows, d, device=self.device) if last else self.ws("tf_x3", (rows, d))
-            self._ffn("d{}_ffn".format(li), x2, x2b, x, xb, "tf_", gemm_tag="tf_ffn_gemm")
+            self._ffn("d{}_ffn".format(li), x2, x2b, x, xb, "tf_", gemm_tag="tf_ffn_gemm", fuse=self.plan.fuse_ln)
         self._last_tf_bf16 = xb
         out = {"hidden_states": x.view(N, t, d) if x is not None else None}
         if want_logits == "all":
@@ -154,7 +148,7 @@ class DecodeMixin:
 
     def decode_full(self, input_ids: torch.Tensor, mem: torch.Tensor, sem: Optional[torch.Tensor],
                     want_logits: str = "all", sem_embs: Optional[torch.Tensor] = None,
-                    want_aux: bool = False, hidden_fp32: bool = True) -> Dict[str, torch.Tensor]:
+                    want_aux: bool = False, hidden_fp32: bool = True, plan: Optional[forms.PassPlan] = None) -> Dict[str, torch.Tensor]:
         """`TransformerDecoder.forward` + `NaiveHead` on whole sequences (Lq = t).
 
         Used by feedforward_step (Framework.py:215-234) and by the stateless
@@ -169,6 +163,8 @@ class DecodeMixin:
         assert N % B == 0 and t <= self.T + 1
         per_clip = N // B
         rows = N * t
+        if plan is None:  # (called on its own: the stateless decoding_phase API)
+            self._begin_pass(self.plan_for(B, rows=rows))
         ids32 = input_ids.to(self.device, torch.int32).contiguous()
         sem_div = 1
         if sem is not None:
@@ -251,7 +247,7 @@ class DecodeMixin:
             out["logits"] = self.gemm(src, w["vocab"], None, torch.empty(N, self.V, device=self.device))
         return out
 
-    def score_teacher_forced(self, input_ids, labels, mem, sem, sem_embs=None):
+    def score_teacher_forced(self, input_ids, labels, mem, sem, sem_embs=None, plan: Optional[forms.PassPlan] = None):
         """Metrics step (crit_lang.py:75-103): per position log p(label) and arg-max token.
 
         bf16 A-stationary path: the vocabulary GEMM keeps running (max, argmax, sum-exp, label
@@ -260,11 +256,13 @@ class DecodeMixin:
         """
         N, t = input_ids.shape
         rows = N * t
+        if plan is None:  # (called on its own, after an encode: metrics_step is the one-pass form)
+            plan = self._begin_pass(self.plan_for(mem.shape[0], rows=rows))
         lab32 = labels.to(self.device, torch.int32).contiguous().view(rows)
         logp = torch.empty(rows, device=self.device)
         pred = torch.empty(rows, device=self.device, dtype=torch.int32)
         if self.bf_act:
-            out = self.decode_full(input_ids, mem, sem, want_logits="none", sem_embs=sem_embs, hidden_fp32=False)
+            out = self.decode_full(input_ids, mem, sem, want_logits="none", sem_embs=sem_embs, hidden_fp32=False, plan=plan)
             xb = self._last_tf_bf16
             parts = self.vocab_parts(rows)
             pm, pi = self.ws("sc_pmax", (rows, parts)), self.ws("sc_pidx", (rows, parts), torch.int32)
@@ -277,7 +275,7 @@ class DecodeMixin:
                  tag="tf_label_logits")
             self.call("care_score_partials_lab", ptr(pm), ptr(pi), ptr(ps), parts, ptr(pl), ptr(logp), ptr(pred), rows)
         else:
-            out = self.decode_full(input_ids, mem, sem, want_logits="all", sem_embs=sem_embs)
+            out = self.decode_full(input_ids, mem, sem, want_logits="all", sem_embs=sem_embs, plan=plan)
             lg = out["logits"].view(rows, self.V)
             self.call("care_score_logits", ptr(lg), lg.stride(0), self.V, ptr(lab32), ptr(logp), ptr(pred), rows)
         return logp.view(N, t), pred.view(N, t)
@@ -288,8 +286,8 @@ class DecodeMixin:
         the log-probability of every label token, the arg-max token, and the encoder outputs (with `preds_attr` for
         the concept metrics).  A model without a concept head encodes lean - nothing of the fp32 memory or the frame
         means is read by the scoring - and no [N * t, V] logits exist at any point."""
-        self._begin_pass()
         feats = self._prep_feats(feats)
+        plan = self._begin_pass(self.plan_for(feats[0].shape[0], rows=input_ids.numel(), lean=not self.has_concepts))
         if (not self.has_concepts and self.tf_fast_ok(input_ids.shape[1], False) and
                 os.environ.get("CARE_TF_OVERLAP", "1") != "0"):
             # Two independent chains meet at the cross-attention: the encoder + the static K / V projection (HBM-leaning: raw
@@ -309,14 +307,14 @@ class DecodeMixin:
                 ckv = self.cross_kv(enc["encoder_hidden_states"], tag="tf_ckv", tile=True)
             self._tf_ckv_ready = (ckv, side)
             try:
-                logp, pred = self.score_teacher_forced(input_ids, labels, enc["encoder_hidden_states"], None)
+                logp, pred = self.score_teacher_forced(input_ids, labels, enc["encoder_hidden_states"], None, plan=plan)
             finally:
                 self._tf_ckv_ready = None
                 cur.wait_stream(side)
             return logp, pred, enc
         enc = self.encode(feats, lean=not self.has_concepts)
         logp, pred = self.score_teacher_forced(input_ids, labels, enc["encoder_hidden_states"], enc.get("semantic_hidden_states"),
-                                               sem_embs=enc.get("semantic_embs"))
+                                               sem_embs=enc.get("semantic_embs"), plan=plan)
         return logp, pred, enc
 
     # ------------------------------------------------------------------ incremental decode step
@@ -330,7 +328,7 @@ class DecodeMixin:
                  ptr(w["word"]), ptr(w["pos"]), t - 1, ptr(sem), rows_per_clip, ptr(w["emb_g"]), ptr(w["emb_be"]),
                  self.eps, ptr(x), ptr(xb), d, N, 1, d)
         g = lambda f32, b16: b16 if b16 is not None else f32  # GEMM input: the bf16 mirror when it exists
-        fuse_ln = self.ln_fusable(self._form_rows or N)  # by the pass's INITIAL row count, not what compaction left
+        fuse_ln = self.plan.fuse_ln  # by the pass's INITIAL row count, not what compaction left
         for li in range(self.n_layers):
             nm = "d{}_sa".format(li)
             cache = skv[li]  # [N, T, 2d]
@@ -357,7 +355,7 @@ class DecodeMixin:
                 # 32-34 us on the A-stationary one, which wins the wider QKV / FFN1 products; decided by the pass's INITIAL
                 # row count like every other choice of form)
                 q2 = self.gemm(x1inb, w[nm + "_q_w"], w[nm + "_q_b"], self.ws(tag + "q2b", (N, d), self.h16),
-                               tag="step_dxd_gemm", tile=d == 512 and (self._form_rows or N) >= self.Q_TILE_MIN_ROWS)
+                               tag="step_dxd_gemm", tile=self.plan.q_tile)
                 qt = self.ws(tag + "qt", (N, H * d), self.h16)
                 if d == 512:
                     self.call("care_head_expand", ptr(q2), d, ptr(w[nm + "_wkt"]), ptr(qt), H * d, N, H, tag="step_head_expand")
@@ -452,7 +450,8 @@ class DecodeMixin:
         g = max(64, cap // 32)
         return min(cap, (active + g - 1) // g * g)
 
-    def greedy_early_exit(self, feats: List[torch.Tensor], lean: bool = False, use_graph: bool = True):
+    def greedy_early_exit(self, feats: List[torch.Tensor], lean: bool = False, use_graph: bool = True,
+                          plan: Optional[forms.PassPlan] = None):
         """encode + greedy decode that STOPS when every clip has ended and drops ended clips from the
         batch on the way (the reference: models/Translator.py:77-81 `if not active_inst_idx_list: break`,
         :194-209 `collect_active_part`; per step and on the host there).
@@ -463,7 +462,7 @@ class DecodeMixin:
         csrc/compact.hip) and the following segments run on that many rows (rounded up to a bucket;
         the padding rows are ended clips that ride along).  Rows are independent end to end and the row-count
         switches of the ENGINE (fused dense+LayerNorm, beam selection form, cross-attention form) are taken from the
-        pass's initial row count (`_form_rows`), so a clip meets the same kernel forms as in the fixed-length pass;
+        pass's initial row count (`self.plan`), so a clip meets the same kernel forms as in the fixed-length pass;
         what still follows the current row count are two tilings INSIDE the library (QKV / FFN1 and the vocabulary
         arg-max move from 256-row to 128-row panels below 8192 rows): the same bf16 products and the same arg-max
         columns, fp32 sums in another order (scores within 1e-4).  A segment is captured into a hipGraph the
@@ -471,13 +470,14 @@ class DecodeMixin:
         fed int32 [B, T + 1] (column 0 = BOS), length int32 [B], score fp32 [B]."""
         feats = self._prep_feats(feats)
         B, T, d = feats[0].shape[0], self.T, self.d
+        if plan is None:  # (called on its own, not from translate_greedy: the segmented multi-launch pass)
+            plan = self._begin_pass(self.plan_for(B, lean=lean, early_exit=True, rows=B))
         # small batches are launch-bound: a segment boundary (one host round trip + one more graph launch,
         # ~40 us) costs as much as several of their steps, so they check twice as rarely and never compact
         S = max(1, self.segment_steps) * (1 if B >= 2048 else 2)
         out_len, out_score, out_fed = self.ws_block("ge_out", [((B,), torch.int32), ((B,), torch.float32), ((B, T + 1), torch.int32)])
         idx = self.ws("ge_idx", (B,), torch.int32)
         cnt = self.ws("ge_cnt", (1,), torch.int32)
-        fkey = (tuple(f.data_ptr() for f in feats), tuple(tuple(f.shape) for f in feats))
         st = {}
 
         def state(par, n):
@@ -515,7 +515,7 @@ class DecodeMixin:
         def first_segment():
             """encode, state initialisation and steps 1 .. S on all B slots of buffer set 0."""
             self._ws_cap = None
-            enc = self.encode(feats, lean, static=True)
+            enc = self.encode(feats, plan.lean, static=True)
             mem = enc["encoder_hidden_states"]
             sem = enc.get("semantic_hidden_states")
             v = state(0, B)
@@ -532,8 +532,7 @@ class DecodeMixin:
         replayable = lambda key, fn: self._replay(key, fn, use_graph)
 
         try:
-            self._form_rows = B
-            enc, v = replayable(("gseg0", self.latent_ok, bool(lean), S) + fkey, first_segment)
+            enc, v = replayable(forms.graph_key("gseg0", plan, feats, S), first_segment)
             par, t = 0, min(S, T) + 1
             stats = dict(clips=B, steps=t - 1, row_steps=B * (t - 1), compactions=0)
             self.last_decode = stats  # what the last pass actually ran (tests, bench)
@@ -548,7 +547,7 @@ class DecodeMixin:
                     stats["compactions"] += 1
                 t1 = min(t + S - 1, T)
                 vv = v
-                replayable(("gseg", par, t, t1, v["n"], B, self.latent_ok), lambda: run_steps(vv, t, t1))
+                replayable(("gseg", plan, t, t1, v["n"], par), lambda: run_steps(vv, t, t1))
                 stats["steps"] = t1
                 stats["row_steps"] += v["n"] * (t1 - t + 1)
                 t = t1 + 1
@@ -608,74 +607,44 @@ class DecodeMixin:
         One pass issues ~360-440 kernel launches (12-15 per step); driven from Python that is
         host-bound, so the whole pass is captured once per (batch, input buffers) into a
         hipGraph (torch.cuda.CUDAGraph on the same stream capture) and replayed.  The graph
-        is keyed on the input pointers: callers that re-use their feature buffers (bench,
+        is keyed on the plan and the input pointers: callers that re-use their feature buffers (bench,
         pinned double-buffered loaders) replay; a first-seen buffer set runs eagerly.
         Returns (enc_outputs, fed, length, score) - static tensors when replayed.
         lean: the caller reads nothing of enc_outputs (the Translator): encode(..., lean=True).
         """
         feats = self._prep_feats(feats)
-        self._begin_pass()
-        lanes = self.lanes_for(feats[0].shape[0]) if use_graph else 1
-        if lanes > 1:
-            return self._translate_greedy_lanes(feats, lanes, lean)
-        ee = self.early_exit if early_exit is None else early_exit
-        if self.resident_ok(feats[0].shape[0]):  # small batch: encode + one resident launch for the whole decode
+        B = feats[0].shape[0]
+        plan = self._begin_pass(self.plan_for(B, lean=lean, early_exit=early_exit, n_lanes=self.lanes_for(B) if use_graph else 1))
+        if plan.lanes > 1:
+            return self._translate_greedy_lanes(feats, plan)
+        if plan.decode == "resident":  # small batch: encode + one resident launch for the whole decode
             def run_resident():
-                self._form_rows = feats[0].shape[0]
-                enc = self.encode(feats, lean, static=True, small=self.small_forms(feats[0].shape[0]))
+                enc = self.encode(feats, plan.lean, static=True, small=plan.small)
                 return (enc,) + tuple(self.greedy_resident(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"),
-                                                           sem_embs=enc.get("semantic_embs"), early_exit=ee))
-            key = ("gres", bool(lean), bool(ee), tuple(f.data_ptr() for f in feats), tuple(tuple(f.shape) for f in feats))
-            try:
-                out = self._replay(key, run_resident, use_graph)
-            except _lib.CareHipError as exc:  # (refused, nothing enqueued: see translate_beam)
-                if "CARE_ESHAPE" not in str(exc):
-                    raise
-                self._note_refused("greedy", feats[0].shape[0])
-                out = None
+                                                           sem_embs=enc.get("semantic_embs"), early_exit=plan.early_exit))
+            out = self._resident_pass("greedy", "gres", feats, run_resident, use_graph, "r_scratch",
+                                      self.lib.care_decode_resident_scratch(B, self.d, self.ff, self.V))
             if out is not None:
-                nb = self.lib.care_decode_resident_scratch(feats[0].shape[0], self.d, self.ff, self.V)
-                self.last_decode = dict(clips=feats[0].shape[0], steps=self.ws("r_scratch", (nb,), torch.uint8)[8:12].view(torch.int32)[0],
-                                        compactions=0, resident=True)
                 return out
-        if ee:
+            plan = self.plan = self.plan_for(B, lean=lean, early_exit=early_exit)  # (refused, and noted: the multi-launch forms)
+        if plan.early_exit:
             # stop when every clip has ended, drop ended clips on the way (greedy_early_exit)
-            return self.greedy_early_exit(feats, lean, use_graph)
+            return self.greedy_early_exit(feats, lean, use_graph, plan=plan)
 
         def run():
-            self._form_rows = feats[0].shape[0]
-            enc = self.encode(feats, lean)
+            enc = self.encode(feats, plan.lean)
             return (enc,) + tuple(self.greedy(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"),
                                               sem_embs=enc.get("semantic_embs")))
 
-        key = ("greedy", self.latent_ok, bool(lean), tuple(f.data_ptr() for f in feats), tuple(tuple(f.shape) for f in feats))
-        return self._replay(key, run, use_graph)
+        return self._replay(forms.graph_key("greedy", plan, feats), run, use_graph)
 
-    def lanes_for(self, B: int) -> int:
-        """Batch lanes of a graph-replayed greedy pass.
-
-        A pass alternates HBM-bound kernels (attention, 44% of the time at B = 16384) with
-        MFMA-bound ones (the GEMMs); two half-batches on two HIP streams inside the one captured
-        graph let the one kind fill the other's idle unit and hide every kernel's tail.  Measured
-        (bf16 Base `ami`, one MI355X): +8% at B = 4096, +5% at 8192/16384; at B <= 2048 the
-        kernels are too short and the extra graph edges cost more than they hide (-3%..-30%), and
-        4 lanes are never better than 2.
-
-        A tuning knob, OFF by default (`self.lanes` = 1; `CARE_LANES` or `engine.lanes = 2` turn it
-        on): with two lanes the kernels share the chip, so per-kernel durations - and with them the
-        roofline accounting of bench.py and profiles/ - no longer describe a kernel on its own.
-        """
-        env = os.environ.get("CARE_LANES")
-        n = int(env) if env else int(self.lanes)
-        return max(1, min(n, B))
-
-    def _translate_greedy_lanes(self, feats, lanes, lean=False):
+    def _translate_greedy_lanes(self, feats, plan):
         """translate_greedy with the batch cut into `lanes` contiguous clip ranges, each with its own
         workspaces and HIP stream, forked from and joined to the capture stream inside ONE hipGraph.
         Clips are independent, so the results are those of the single-lane pass."""
-        B = feats[0].shape[0]
+        B, lanes = plan.clips, plan.lanes
         bounds = [(B * i // lanes, B * (i + 1) // lanes) for i in range(lanes)]
-        if len(getattr(self, "_lane_streams", ())) < lanes:
+        if len(self._lane_streams) < lanes:
             self._lane_streams = [torch.cuda.Stream(device=self.device) for _ in range(lanes)]
 
         def run():
@@ -687,16 +656,16 @@ class DecodeMixin:
                     st.wait_stream(cur)
                     with torch.cuda.stream(st):
                         self._lane = i + 1  # workspace namespace of this lane (see ws)
-                        enc = self.encode([f[lo:hi] for f in feats], lean)
+                        self.plan = self.plan_for(hi - lo, lean=plan.lean, early_exit=False, rows=hi - lo)  # (a lane's forms: by ITS rows)
+                        enc = self.encode([f[lo:hi] for f in feats], plan.lean)
                         parts.append((enc,) + tuple(self.greedy(enc["encoder_hidden_states"],
                                                                 enc.get("semantic_hidden_states"),
                                                                 sem_embs=enc.get("semantic_embs"))))
             finally:
-                self._lane = 0
+                self._lane, self.plan = 0, plan
             for st in self._lane_streams[:lanes]:
                 cur.wait_stream(st)
             return (_LaneOutputs([pt[0] for pt in parts]),) + tuple(torch.cat([pt[k] for pt in parts], 0)
                                                                      for k in (1, 2, 3))
 
-        key = ("greedy", lanes, self.latent_ok, bool(lean), tuple(f.data_ptr() for f in feats), tuple(tuple(f.shape) for f in feats))
-        return self._replay(key, run, True)
+        return self._replay(forms.graph_key("greedy", plan, feats), run, True)

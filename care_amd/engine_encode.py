@@ -2,14 +2,14 @@
 container - reference models/Framework.py:150-187, Encoder.py, Predictor/pred_attribute.py), the static keys / values of the
 cross-attention (projected once per clip, or the absorbed form's bf16 memory).  Methods of care_amd.engine.HipEngine."""
 import contextlib
+import functools
 import ctypes
-import os
 import weakref
 from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, forms
 from ._lib import ACT_CODES, CARE_BF16, CARE_F32, ptr
 from .constants import BOS, EOS, PAD
 from .engine_util import _LaneOutputs
@@ -17,14 +17,12 @@ from .engine_util import _LaneOutputs
 
 class EncodeMixin:
     # ------------------------------------------------------------------ encoder + concept head
-    @property
+    @functools.cached_property
     def lean_ok(self) -> bool:
         """The captioning loop of a model WITHOUT a concept head consumes nothing of the encoder but the
         bf16 memory (the A operand of the cross-K/V projection, or what the absorbed cross-attention
         reads).  `encode(..., lean=True)` then skips what nobody reads: the fp32 copy of the memory
         (5.6 GB of stores at B = 32768) and the per-modality frame means (a second pass over it)."""
-        if os.environ.get("CARE_LEAN", "1") == "0":  # A/B switch
-            return False
         return (self.as_ok and self.d == 512 and not self.has_concepts and self.opt["encoder"] == "Embedder" and
                 all(ch in self.dec_mod and int(self.opt["dim_" + ch]) % 32 == 0 for ch in self.modality))
 
@@ -93,20 +91,16 @@ class EncodeMixin:
                 if small and fused and (Ws is None or w.get("enc_w_" + ch + "#split3") is not None):
                     # (concept models: the split products through the LDS-tiled kernel, below) - unless the loader-wave
                     # kernel takes the rows (version 3 of csrc/gemm_ln.hip: whole 128-row blocks, FUSED_SMALL_MIN_ROWS of them)
-                    fused = (B * n) % 128 == 0 and B * n >= self.FUSED_SMALL_MIN_ROWS and x2.shape[1] % 128 == 0
+                    fused = (B * n) % 128 == 0 and B * n >= forms.FUSED_SMALL_MIN_ROWS and x2.shape[1] % 128 == 0
                 W3 = w.get("enc_w_" + ch + "#split3")
                 if fused:
                     lin = None
                 elif W3 is not None:
-                    lin = self.ws("enc_lin" + sfx, (B * n, d))
-                    if os.environ.get("CARE_ENC_TILE", "1") != "0":  # fp16 pieces of the features once, then the LDS-tiled kernel
-                        a2 = self.ws("enc_a2" + sfx, (B * n, 2 * x2.shape[1]), torch.float16)
-                        self.call("care_split2_act", ptr(x2), x2.stride(0), ptr(a2), B * n, x2.shape[1], tag="enc_split")
-                        self.call("care_gemm_tile_split3", ptr(a2), ptr(W3), ptr(w["enc_b_" + ch]), ptr(lin), lin.stride(0), CARE_F32,
-                             None, 0, 0, d, B * n, d, x2.shape[1], 0, tag="enc_gemm")
-                    else:
-                        self.call("care_gemm_split3", ptr(x2), x2.stride(0), ptr(W3), ptr(w["enc_b_" + ch]), ptr(lin), lin.stride(0),
-                             B * n, d, x2.shape[1], tag="enc_gemm")
+                    lin = self.ws("enc_lin" + sfx, (B * n, d))  # fp16 pieces of the features once, then the LDS-tiled kernel
+                    a2 = self.ws("enc_a2" + sfx, (B * n, 2 * x2.shape[1]), torch.float16)
+                    self.call("care_split2_act", ptr(x2), x2.stride(0), ptr(a2), B * n, x2.shape[1], tag="enc_split")
+                    self.call("care_gemm_tile_split3", ptr(a2), ptr(W3), ptr(w["enc_b_" + ch]), ptr(lin), lin.stride(0), CARE_F32,
+                         None, 0, 0, d, B * n, d, x2.shape[1], 0, tag="enc_gemm")
                 else:
                     lin = self.gemm(x2, w["enc_w_" + ch], w["enc_b_" + ch], self.ws("enc_lin" + sfx, (B * n, d)), tag="enc_gemm")
                 in_mem = ch in self.dec_mod
@@ -213,30 +207,11 @@ class EncodeMixin:
                                  tile=src2.dtype == self.h16 and (tile or (resident and self.RESIDENT_CKV_TILE_ROWS >= 0))))
         return out
 
-    LATENT_MIN_ROWS = 1
-
-    def latent_for(self, rows: int) -> bool:
-        """Absorbed cross-attention for a decode over `rows` rows?  The FORM OF THE ARITHMETIC is a
-        property of the model and its compute mode (bf16, d_model = 512: absorbed; otherwise projected
-        K/V), NOT of the batch a clip happens to be in: the two forms are two bf16 roundings of the same
-        algebra, and switching between them by row count (round 1: from 2048 rows) made a clip's
-        caption depend on the size of its batch wherever two tokens were nearly tied.  The price: the
-        absorbed form has two more launches per step, which small, launch-bound batches feel
-        (*measured* round 1: -15% at 32 rows, -1% at 1024; +5% at 2048, +13% at 16384).
-        `engine.latent = False` (CARE_LATENT=0) selects projected K/V for every size instead;
-        LATENT_MIN_ROWS > 1 restores a row threshold (tuning only).
-        This is the MULTI-LAUNCH decode.  Greedy batches of <= resident_max_rows clips (256) take the resident decode
-        instead (resident_ok): one launch, projected K/V - a deliberate exception to the rule above, bought with
-        2 x the small-batch step rate; `resident_max_rows = 0` restores one form at every size."""
-        return self.latent_ok and rows >= self.LATENT_MIN_ROWS and not getattr(self, "_small_pass", False)
-
-    Q_TILE_MIN_ROWS = int(os.environ.get("CARE_Q_TILE_MIN_ROWS", "8192"))
-
     def cross_src(self, mem: torch.Tensor, rows: int):
         """What the decoder's cross-attention reads at every step: per-layer projected K/V
         (cross_kv, a list of [B*Lk, 2d] tensors), or - absorbed form - the bf16 memory itself
-        ([B, Lk, d], shared by all layers; a tuple marks it)."""
-        if not self.latent_for(rows):
+        ([B, Lk, d], shared by all layers; a tuple marks it) - as the pass planned (forms.latent)."""
+        if not self.plan.latent:
             return self.cross_kv(mem)
         mem = mem.contiguous()
         if mem.dtype == self.h16:  # lean encode: the bf16 memory is all there is

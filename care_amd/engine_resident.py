@@ -1,13 +1,13 @@
-"""HipEngine, the small-batch forms: which batches decode as ONE resident launch (csrc/decode_resident*.hip) or as chained
-kernels per step (csrc/decode_chain.hip), and their drivers (models/Translator.py:77-143 on the device).  Methods of
-care_amd.engine.HipEngine."""
+"""HipEngine, the small-batch forms: the drivers of the decode as ONE resident launch (csrc/decode_resident*.hip) and as
+chained kernels per step (csrc/decode_chain.hip) (models/Translator.py:77-143 on the device); which batches take them is
+care_amd/forms.py's.  Methods of care_amd.engine.HipEngine."""
 import ctypes
 import os
 from typing import Dict, List, Optional
 
 import torch
 
-from . import _lib
+from . import _lib, forms
 from ._lib import ACT_CODES, CARE_BF16, CARE_F32, ptr
 from .constants import BOS, EOS, PAD
 from .engine_util import _LaneOutputs, device_props
@@ -15,89 +15,22 @@ from .engine_util import _LaneOutputs, device_props
 
 class ResidentMixin:
     # ------------------------------------------------------------------ resident decode of small batches
-    RESIDENT_MAX_V = 64 * 64 * 4  # csrc/decode_resident.hip: 64 lanes x RES_NP column-group partials of 64 columns
-
-    def resident_ok(self, rows: int) -> bool:
-        """Greedy decode of `rows` clips as one resident launch (csrc/decode_resident.hip)?  bf16 mode, d_model = 512;
-        a form of its own next to the multi-launch one: projected cross K/V, the same rounding points, sums in another
-        order - so which of two nearly tied tokens wins can differ between a batch of <= resident_max_rows clips and a
-        larger one (the audit of tests/test_gpu_properties.py counts such rows)."""
-        if not (0 < rows <= self.resident_max_rows and self._resident_model_ok()):
-            return False
-        if rows >= self._refused_from("greedy"):
-            return False
-        if self.d != 512 and rows > self.RESIDENT_WIDE_MAX_ROWS:
-            return False
-        return self._resident_fits(rows)
-
-    RESIDENT_WIDE_MAX_ROWS = 128  # d_model 768 / 1024: the K-split forms only (csrc/decode_resident.hip, template D)
-
-    def _resident_model_ok(self, beam: bool = False) -> bool:
-        """Every model-side limit care_decode_resident / care_decode_resident_beam enforce (CARE_ESHAPE otherwise):
-        bf16 mode; d_model 512 (ff 512 / 1024 / 2048), or - greedy only - d_model 768 / 1024 with ff = 4 d_model."""
-        if self.pre_ln:  # (the resident phases normalise AFTER the residual sum: post-LN decoders only)
-            return False
-        if not (self.bf and self.wt == self.h16 and self.T <= 128 and self.n_layers <= 4 and
-                (not self.attr_att or self.topk <= 128) and self.V <= self.RESIDENT_MAX_V and self.Lk <= 128):
-            return False
-        if self.d == 512:
-            return bool(self.as_ok and self.ff in (512, 1024, 2048))
-        return bool(self.d in (768, 1024) and self.ff == 4 * self.d and self.bf_act)  # (greedy and - round 5 - beam search)
-
-    def _refused_from(self, kind: str) -> int:
-        """Smallest row count at which a resident launch of `kind` ("greedy" / "beam") was refused on this device
-        (CARE_ESHAPE: fewer co-resident workgroups than the launch needs - a partition with few CUs); launches below it are
-        still tried, the chained step (no residency condition) never looks here."""
-        return getattr(self, "_resident_refused", {}).get(kind, 1 << 30)
-
-    def _note_refused(self, kind: str, rows: int) -> None:
-        d = self.__dict__.setdefault("_resident_refused", {})
-        d[kind] = min(d.get(kind, 1 << 30), rows)
-
-    def _resident_fits(self, rows: int, per_tile: int = 1) -> bool:
-        """one workgroup per CU at most, and at least one per group of `per_tile` 16-row tiles (a partitioned GPU has fewer CUs)"""
-        if self.device is not None and torch.cuda.is_available():
-            if getattr(self, "_cus", None) is None:
-                self._cus = device_props(self.device).multi_processor_count
-            return ((rows + 15) // 16 + per_tile - 1) // per_tile <= self._cus // 8 * 8
-        return True
-
-    RESIDENT_BEAM_MAX = 8  # csrc/decode_resident.h RES_BMK: 5 in the launch's first instance, 8 in its second (decode_resident_beam_wide.hip)
-    # beam search of the d_model 768 / 1024 models as one resident launch up to this many rows (160 at d_model 1024).  *Measured*
-    # (round 5, tools/beam_sweep.py, us per step of the whole pass, resident / multi-launch): d_model 1024 - 5 rows 103 / 207, 40
-    # rows 131 / 214, 125 rows 171 / 225, 160 rows 196 / 225, 200 rows 232 / 228; d_model 768 - 5 rows 88 / 186, 160 rows 152 / 202,
-    # 255 rows 183 / 207
-    RESIDENT_WIDE_BEAM_MAX_ROWS = int(os.environ.get("CARE_RESIDENT_WIDE_BEAM_MAX_ROWS", "256"))
-
-    def resident_beam_ok(self, clips: int, bm: int, need: int) -> bool:
-        """Beam search over `clips` clips as one resident launch (csrc/decode_resident_beam.hip)?  The limits of
-        care_decode_resident_beam: the greedy launch's, beam_size <= 8, a hypothesis' positions one per lane (T <= 63)."""
-        rows = clips * bm
-        if not (0 < rows <= self.resident_beam_max_rows and 1 < bm <= self.RESIDENT_BEAM_MAX and need >= 1 and
-                self._resident_model_ok(beam=True) and self.T <= 63 and self.V >= 16 * self.RESIDENT_BEAM_MAX):
-            return False
-        if rows >= self._refused_from("beam"):
-            return False
-        if self.d != 512 and rows > (self.RESIDENT_WIDE_BEAM_MAX_ROWS if self.d <= 768 else min(160, self.RESIDENT_WIDE_BEAM_MAX_ROWS)):
-            return False  # (d_model 768 / 1024: the K-split forms; see RESIDENT_WIDE_BEAM_MAX_ROWS)
-        # (care_decode_resident_beam packs two row tiles per workgroup only in its forms for MORE than 512 rows; up to 512
-        # rows it needs a workgroup per 16-row tile - a partitioned device with fewer CUs than tiles must not be promised
-        # the resident form: ADVICE r4)
-        return self._resident_fits(rows, 2 if rows > 512 else 1)
-
-    def chain_beam_ok(self, clips: int, bm: int, need: int) -> bool:
-        """Beam search over `clips` clips with every step a chain of kernels (csrc/decode_chain.hip)?  The model-side
-        limits of the resident beam launch (its phases are the chain's kernels); no residency condition, so the row
-        count is bounded only by where the large-batch forms take over (`chain_beam_max_rows`)."""
-        rows = clips * bm
-        return bool(0 < rows <= self.chain_beam_max_rows and 1 < bm <= 5 and need >= 1 and self.d == 512 and   # (RES_BMK of decode_chain.hip)
-                    self._resident_model_ok(beam=True) and self.T <= 63 and self.V >= 16 * self.RESIDENT_BEAM_MAX)
-
-    def small_forms(self, clips: int) -> bool:
-        """Batches of <= resident_max_rows clips (bf16, d_model = 512) take the small-batch forms of the pass: the
-        embedder as GEMM + LayerNorm launches side by side per modality (encode(small=True)) and, for greedy decoding,
-        the resident decode.  `resident_max_rows = 0`: one set of forms at every batch size."""
-        return 0 < clips <= self.resident_max_rows and self.as_ok and self.d == 512
+    def _resident_pass(self, kind: str, name: str, feats, run, use_graph: bool, scratch: str, nbytes: int, **stats):
+        """A pass whose decode is ONE resident launch of `kind` ("greedy" / "beam"): run() through the graph cache, or None
+        where the launch was refused before anything was enqueued (CARE_ESHAPE: the device admits fewer resident workgroups
+        than the launch needs - a partition with few CUs, another occupancy).  The refusal is noted (forms.resident_fits), so
+        the next plan of this engine takes the multi-launch forms from that row count on: not an error."""
+        plan = self.plan
+        try:
+            out = self._replay(forms.graph_key(name, plan, feats), run, use_graph)
+        except _lib.CareHipError as exc:
+            if "CARE_ESHAPE" not in str(exc):
+                raise
+            self._resident_refused[kind] = min(self._resident_refused.get(kind, 1 << 30), plan.rows)
+            return None
+        self.last_decode = dict(clips=plan.clips, steps=self.ws(scratch, (nbytes,), torch.uint8)[8:12].view(torch.int32)[0],
+                                compactions=0, resident=True, **stats)
+        return out
 
     def _resident_layers(self, tag: str, rows: int, rows_per_clip: int, ckv, akv, Lk: int):
         """care_resident_layer[] of this model for a resident launch over `rows` rows (self-attention caches in the
@@ -144,8 +77,7 @@ class ResidentMixin:
         self.call("care_decode_resident_beam", ctypes.addressof(layers), self.n_layers, ptr(w["word"]), ptr(w["pos"]), ptr(sem),
              ptr(w["emb_g"]), ptr(w["emb_be"]), self.eps, ptr(w["vocab"]), self.V, d, self.H, self.ff, self.act, B, bm, need, T, T,
              BOS, EOS, PAD, ptr(tok), T + 1, ptr(anc[0]), ptr(anc[1]), ptr(scores), ptr(done), ptr(nfin), ptr(fscore), ptr(flen),
-             ptr(fhyp), cap, ptr(scratch), nbytes, int(bool(early_exit)), int(os.environ.get("CARE_RESIDENT_BLOCKS", "0")),
-             tag="decode_resident_beam")
+             ptr(fhyp), cap, ptr(scratch), nbytes, int(bool(early_exit)), 0, tag="decode_resident_beam")
         self.last_decode = dict(clips=B, steps=scratch[8:12].view(torch.int32)[0], compactions=0, resident=True,
                                 row_steps=None)
         return nfin, fscore, flen, fhyp
@@ -187,26 +119,24 @@ class ResidentMixin:
         return v
 
     def translate_beam_chain(self, feats: List[torch.Tensor], bm: int, need: int, use_graph: bool = True, lean: bool = False,
-                             early_exit: bool = True):
+                             early_exit: bool = True, plan: Optional[forms.PassPlan] = None):
         """encode + beam search with chained steps.  The pass runs in segments of `chain_segment_steps` steps, each a
         hipGraph of its own (the first with the encoder and the static K/V projection); between segments the host reads
         ONE counter - the clips still live - and stops when none is (`if not active_inst_idx_list: break`,
         models/Translator.py:77-81).  early_exit=False: all T steps in one graph.  No compaction: the chain serves the
         row counts below those at which moving the survivors pays (engine.beam_early_exit)."""
         B, T = feats[0].shape[0], self.T
+        if plan is None:  # (called on its own, not from translate_beam)
+            plan = self._begin_pass(self.plan_for(B, bm, need, lean=lean, early_exit=early_exit))
         S = max(1, self.chain_segment_steps) if early_exit else T
-        fkey = (tuple(f.data_ptr() for f in feats), tuple(tuple(f.shape) for f in feats))
-        box = {}
 
         def first():
-            self._form_rows = B * bm
-            enc = self.encode(feats, lean, static=True, small=self.small_forms(B))
-            box["enc"] = enc
+            enc = self.encode(feats, plan.lean, static=True, small=plan.small)
             v = self.beam_chain_steps(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"), bm, need, 1, min(S, T),
                                       sem_embs=enc.get("semantic_embs"), count_live=early_exit)
             return enc, v
 
-        enc, v = self._replay(("bchain", 0, S, bm, need, bool(lean), bool(early_exit)) + fkey, first, use_graph)
+        enc, v = self._replay(forms.graph_key("bchain", plan, feats, 0, S), first, use_graph)
         t = min(S, T) + 1
         stats = dict(clips=B, steps=t - 1, row_steps=B * bm * (t - 1), compactions=0, chain=True)
         self.last_decode = stats
@@ -215,7 +145,7 @@ class ResidentMixin:
                 break
             t1 = min(t + S - 1, T)
             tt = t
-            self._replay(("bchain", tt, t1, bm, need, B, bool(lean)) + fkey,
+            self._replay(forms.graph_key("bchain", plan, feats, tt, t1),
                          lambda: self.beam_chain_steps(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"), bm, need,
                                                        tt, t1, sem_embs=enc.get("semantic_embs")), use_graph)
             stats["steps"] = t1
@@ -243,6 +173,6 @@ class ResidentMixin:
         self.call("care_decode_resident", ctypes.addressof(layers), self.n_layers, ptr(w["word"]), ptr(w["pos"]), ptr(sem), 1,
              ptr(w["emb_g"]), ptr(w["emb_be"]), self.eps, ptr(w["vocab"]), self.V, d, self.H, self.ff, self.act, B, T, steps,
              BOS, EOS, PAD, ptr(fed), T + 1, ptr(score), ptr(length), ptr(fin), ptr(scratch), nbytes,
-             int(bool(early_exit)), int(os.environ.get("CARE_RESIDENT_BLOCKS", "0")), tag="decode_resident")
+             int(bool(early_exit)), 0, tag="decode_resident")
         self.last_decode = dict(clips=B, steps=scratch[8:12].view(torch.int32)[0], compactions=0, resident=True)
         return fed, length, score

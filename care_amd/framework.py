@@ -384,7 +384,7 @@ class TransformerSeq2Seq(nn.Module):
         n_mod = len(self.opt["modality"])
         with torch.no_grad(), self._on_device(), self.engine().lock:
             eng = self.engine()
-            eng._begin_pass()
+            eng._begin_pass(eng.plan_for(feats[0].shape[0]))
             out = eng.encode(list(feats[:n_mod]))
         if self.predictor is not None:
             out["attribute_prediction_prj"] = self.predictor.nets[0].prj
@@ -413,10 +413,10 @@ class TransformerSeq2Seq(nn.Module):
         aux = kwargs.get("output_auxiliary", not last_time_step_logits)
         with torch.no_grad(), self._on_device(), self.engine().lock:
             eng = self.engine()
-            eng._begin_pass()
+            plan = eng._begin_pass(eng.plan_for(mem.shape[0], rows=input_ids.numel()))
             return eng.decode_full(input_ids, mem, inputs_for_decoder.get("semantic_hidden_states"),
                                              want_logits="last" if last_time_step_logits else "all",
-                                             sem_embs=inputs_for_decoder.get("semantic_embs"), want_aux=bool(aux))
+                                             sem_embs=inputs_for_decoder.get("semantic_embs"), want_aux=bool(aux), plan=plan)
 
     def feedforward_step(self, batch: Dict[str, Any], **kwargs) -> Dict[str, Any]:
         if self.training:

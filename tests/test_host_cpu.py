@@ -422,9 +422,10 @@ def test_small_batch_form_rules(monkeypatch):
     assert base.resident_ok(1) and base.resident_ok(256) and not base.resident_ok(257) and not base.resident_ok(0)
     assert base.small_forms(128) and not base.small_forms(320)
     assert all(base.latent_for(r) for r in (1, 640, 1 << 20))          # the multi-launch form: absorbed at every size
-    base._small_pass = True                                            # ... except inside a small beam pass
-    assert not base.latent_for(640)
-    base._small_pass = False
+    base.plan = base.plan_for(128, 5, 5)                               # ... except inside a small beam pass
+    assert base.plan.small_beam and not base.latent_for(640)
+    base.plan = base.plan_for(129)
+    assert base.latent_for(640)
     base.resident_max_rows = 0
     assert not base.resident_ok(1) and not base.small_forms(1)
     for cfg, dtype in (("msrvtt_base_ami", "fp32"), ("msrvtt_care", "fp16x3"), ("vatex_care_large", "fp32")):

@@ -29,7 +29,7 @@ def main():
     labels = torch.randint(4, opt["vocab_size"], (B, T), generator=gen, device=dev)
 
     def score():
-        eng._begin_pass()
+        eng._begin_pass(eng.plan_for(B))
         enc = eng.encode(feats)
         return eng.score_teacher_forced(ids, labels, enc["encoder_hidden_states"], enc.get("semantic_hidden_states"),
                                         sem_embs=enc.get("semantic_embs"))
