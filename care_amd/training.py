@@ -409,7 +409,15 @@ class _Attention(torch.autograd.Function):
 
 
 class _Seeds:
-    """One 64-bit seed per dropout site and call, derived from torch's generator (torch.manual_seed reproduces a run)."""
+    """One 64-bit seed per dropout site and call, derived from torch's generator (torch.manual_seed reproduces a run).
+
+    Site n's seed is a HASH of (base, n) - the splitmix64 finaliser over base + G n - not the stepped value itself: the
+    kernels' generator (csrc/backward.hip, b_uniform) hashes seed + G (index + 1) with the same increment G, so with stepped
+    seeds element i of site n + s and element i + s of site n hashed the same 64-bit value - the masks of neighbouring sites (the
+    attention probabilities and the hidden dropout behind them) were shifted copies of one another
+    (tests/test_gpu_backward_kernels.py, test_dropout_masks_of_different_sites_are_independent)."""
+
+    _M64 = (1 << 64) - 1
 
     def __init__(self):
         self.base = int(torch.randint(0, 2 ** 62, (1,)).item())
@@ -417,7 +425,10 @@ class _Seeds:
 
     def next(self) -> int:
         self.n += 1
-        return (self.base + 0x9E3779B97F4A7C15 * self.n) % (2 ** 63)
+        z = (self.base + 0x9E3779B97F4A7C15 * self.n) & self._M64
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & self._M64
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & self._M64
+        return (z ^ (z >> 31)) % (2 ** 63)
 
 
 def training_forward(model, batch: Dict[str, Any], **kwargs) -> Dict[str, Any]:
