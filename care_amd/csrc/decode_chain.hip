@@ -23,6 +23,7 @@
 // (Beam.advance and its quirks), models/components/Layers.py:157-228 (DecoderLayer), Head.py:26-32.
 #define RES_PLAIN_IO 1
 #include "decode_beam_phase.h"
+#include "decode_launch.h"
 
 namespace {
 
@@ -80,18 +81,6 @@ inline int gemm_grid(int RG, int CI, int nsl_cap) {
   return 8 * RG * nsl;
 }
 
-struct ChainKnobs {
-  int cfg, shared_min;  // -1: not set
-  ChainKnobs() {
-    auto geti = [](const char* n) { const char* e = getenv(n); return e ? atoi(e) : -1; };
-    cfg = geti("CARE_CHAIN_CFG"); shared_min = geti("CARE_CHAIN_SHARED_MIN_ROWS");
-  }
-};
-inline const ChainKnobs& chain_knobs() {
-  static const ChainKnobs k;
-  return k;
-}
-
 }  // namespace
 
 extern "C" {
@@ -106,60 +95,35 @@ int care_decode_chain_beam(const care_resident_layer* layers, int n_layers, cons
                            int bos, int eos, int pad, int32_t* tok, int stride, int32_t* anc0, int32_t* anc1,
                            float* scores, int32_t* done, int32_t* nfin, float* fscore, int32_t* flen, int32_t* fhyp,
                            int fin_cap, void* scratch, int64_t scratch_bytes, int form, void* stream) {
-  if (!layers || !word || !pos || !emb_g || !emb_b || !vocab_w || !tok || !anc0 || !anc1 || !scores || !done || !nfin ||
-      !fscore || !flen || !fhyp || !scratch)
-    return CARE_EINVAL;
-  if (n_layers < 1 || n_layers > RES_MAX_LAYERS || clips < 1 || beam < 1 || need < 1 || fin_cap < 1 || T < 1 || t0 < 1 ||
-      t1 < t0 || t1 > T || V < 1 || stride < T + 1)
-    return CARE_EINVAL;
+  const ResModel m{layers, n_layers, word, pos, sem, emb_g, emb_b, eps, vocab_w, V, d, heads, ff, act, T, stride, scratch, scratch_bytes};
   // (the limits of the resident beam launch's phases: a hypothesis' positions one per lane, a clip's candidates one per
   // lane, RES_BMK groups per row; no limit on the rows)
-  if (d != 512 || heads * 64 != d || (ff != 512 && ff != 1024 && ff != 2048) || T > 63 || V > 64 * 64 * RES_NP || beam > RES_BMK ||
-      V < 4 * RES_BMK * 4)
-    return CARE_ESHAPE;
-  if (act < CARE_ACT_NONE || act > CARE_ACT_GELU) return CARE_EDTYPE;
-  if (scratch_bytes < care_decode_chain_beam_scratch(clips, beam, d, ff, V) || !care_aligned16(scratch)) return CARE_EINVAL;
+  if (const int rc = res_check(m, tok && anc0 && anc1 && scores && done && nfin && fscore && flen && fhyp,
+                               clips >= 1 && beam >= 1 && need >= 1 && fin_cap >= 1 && t0 >= 1 && t1 >= t0 && t1 <= T,
+                               d == 512 && T <= 63 && beam <= RES_BMK && V >= 4 * RES_BMK * 4,
+                               care_decode_chain_beam_scratch(clips, beam, d, ff, V)))
+    return rc;
   const int64_t rows64 = (int64_t)clips * beam;
   if (rows64 > (1 << 20)) return CARE_ESHAPE;
   const int rows = (int)rows64;
   RArgs p{};
-  if (const int rc = res_fill_layers(p, layers, n_layers)) return rc;
+  if (const int rc = res_fill(p, m, beam, rows, t1, bos, eos, pad, 0, false)) return rc;
   for (int l = 0; l < n_layers; ++l)
     for (int a = 0; a < p.L[l].n_att; ++a)
       if (p.L[l].att[a].rows_per_kv != beam) return CARE_EINVAL;  // the beams of a clip share its static keys
-  p.word = word; p.pos = pos; p.sem = sem; p.sem_div = beam; p.emb_g = emb_g; p.emb_be = emb_b; p.eps = eps;
-  p.vocab = (const bf16_t*)vocab_w; p.V = V;
-  p.d = d; p.H = heads; p.ff = ff; p.act = act; p.R = rows; p.T = T; p.steps = t1; p.bos = bos; p.eos = eos; p.pad = pad; p.early = 0;
-  p.prof_step = 0; p.ghost = 0; p.fenced = 0;
   p.fed = tok; p.fed_stride = stride; p.score = scores; p.length = nullptr; p.fin = nullptr;
   p.bm = beam; p.nclips = clips; p.need = need; p.fin_cap = fin_cap;
   p.anc[0] = anc0; p.anc[1] = anc1; p.done = done; p.nfin = nfin; p.fscore = fscore; p.flen = flen; p.fhyp = fhyp;
-  const int64_t R16 = ((int64_t)rows + 15) / 16 * 16;
-  int64_t maxparts = (V + 63) / 64;
-  if (maxparts > 64 * RES_NP) maxparts = 64 * RES_NP;
-  unsigned char* b = (unsigned char*)scratch;
-  p.sync = (unsigned*)b; b += RES_SYNC_BYTES;  // (word 1: clips done - the advance kernel's counter)
-  p.xres = (float*)b; b += R16 * d * 4;
-  p.y = (float*)b; b += R16 * d * 4;
-  p.y2 = (float*)b; b += R16 * d * 4;
-  p.q = (float*)b; b += R16 * d * 4;
-  p.ctx = (bf16_t*)b; b += R16 * d * 2;
-  p.h = (bf16_t*)b; b += R16 * ff * 2;
-  p.pmax = (float*)b; b += R16 * maxparts * 4;
-  p.pidx = (int32_t*)b; b += R16 * maxparts * 4;
-  p.psum = (float*)b; b += R16 * maxparts * 4;
-  p.gval = (float*)b; b += R16 * maxparts * RES_BMK * 4;
-  p.ggid = (int32_t*)b; b += R16 * maxparts * RES_BMK * 4;
-  p.hn = (bf16_t*)b; b += R16 * d * 2;
-  p.xa = (bf16_t*)b;
+  res_layout(&p, (unsigned char*)scratch, rows, d, ff, V, true);  // (of sync, word 1 only: clips done - the advance kernel's counter)
+  const int64_t R16 = ((int64_t)rows + 15) / 16 * 16, maxparts = res_max_parts(d, V);
 
   // Forms by row count (CARE_CHAIN_CFG / `form` >= 0 force one), the resident beam launch's (same bits in every form of a
   // phase, see gemm_phase): 0 (<= 64 rows) K-split items everywhere, FFN dense2 over two workgroups per column tile;
   // 1 one row tile per workgroup, 64-column items for QKV / FFN dense1 / vocabulary (two row tiles per vocabulary fetch
   // from 128 rows); 3 two row tiles per weight fetch in QKV / the N = 512 products / FFN dense1, four in the vocabulary.
-  const ChainKnobs& kn = chain_knobs();
+  const ResKnobs& kn = res_knobs();
   int cfg = rows <= 64 ? 0 : rows <= 256 ? 1 : 3;
-  if (kn.cfg >= 0 && kn.cfg <= 3) cfg = kn.cfg;
+  if (kn.chain_cfg >= 0 && kn.chain_cfg <= 3) cfg = kn.chain_cfg;
   if (form >= 0 && form <= 3) cfg = form;
   if (cfg == 2) cfg = 3;
   if (ff != 2048) cfg = 0;  // (one form for the narrow FFNs)
@@ -174,7 +138,7 @@ int care_decode_chain_beam(const care_resident_layer* layers, int n_layers, cons
   p.vcap = 0;
   p.parts = 8 * nsl_v < CIV ? 8 * nsl_v : CIV;
   if (p.parts > maxparts || p.parts < 1) return CARE_ESHAPE;
-  const int shared_min = kn.shared_min >= 0 ? kn.shared_min : 128;  // rows from which the beams of a clip share a K/V fetch
+  const int shared_min = kn.chain_shared_min >= 0 ? kn.chain_shared_min : 128;  // rows from which the beams of a clip share a K/V fetch
   const bool shared = beam > 1 && rows >= shared_min;
 
   hipStream_t st = (hipStream_t)stream;

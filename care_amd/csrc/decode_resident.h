@@ -1691,8 +1691,7 @@ RES_PHASE_FN unsigned attn_shared_phase(const RArgs& p, GridSync& gs, bool do_wa
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Host side, shared by care_decode_resident and care_decode_resident_beam.
-
+// Host side: decode_launch.h.  Here only the kernel it runs in front of every resident launch (res_zero_words).
 // The launch's sync area is zeroed by a KERNEL of our own in front of it, not by hipMemsetAsync: captured into a hipGraph, the
 // memset node of ROCm 7.2 replays - from the second replay of some graphs on (the d_model 768 / 1024 greedy passes whose input
 // tensors had been freed and allocated again between replays: *measured* round 6) - as a fill with a 16-BYTE PATTERN OF TWO
@@ -1702,94 +1701,6 @@ RES_PHASE_FN unsigned attn_shared_phase(const RArgs& p, GridSync& gs, bool do_wa
 __global__ void res_zero_kernel(unsigned* p, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = 0u;
-}
-inline hipError_t res_zero_words(unsigned* p, int bytes, hipStream_t st) {
-  hipLaunchKernelGGL(res_zero_kernel, dim3((bytes / 4 + 255) / 256), dim3(256), 0, st, p, bytes / 4);
-  return hipGetLastError();
-}
-
-// care_resident_layer[] -> RArgs::L; 0 or a CARE_E* code
-inline int res_fill_layers(RArgs& p, const care_resident_layer* layers, int n_layers) {
-  for (int l = 0; l < n_layers; ++l) {
-    const care_resident_layer& s = layers[l];
-    RLayer& L = p.L[l];
-    if (!s.qkv_w || !s.qkv_b || !s.o_w || !s.o_b || !s.ln_g || !s.ln_b || !s.self_kv || !s.w1 || !s.b1 || !s.w2 || !s.b2 ||
-        !s.ffn_g || !s.ffn_b || s.n_att < 0 || s.n_att > 2)
-      return CARE_EINVAL;
-    L.qkv_w = (const bf16_t*)s.qkv_w; L.qkv_b = s.qkv_b; L.o_w = (const bf16_t*)s.o_w; L.o_b = s.o_b; L.g = s.ln_g; L.be = s.ln_b;
-    L.skv = (bf16_t*)s.self_kv;
-    L.n_att = s.n_att;
-    for (int a = 0; a < s.n_att; ++a) {
-      const care_resident_attn& sa = s.att[a];
-      if (!sa.q_w || !sa.q_b || !sa.o_w || !sa.o_b || !sa.ln_g || !sa.ln_b || !sa.kv || sa.rows_per_kv < 1) return CARE_EINVAL;
-      if (sa.nkeys < 1 || sa.nkeys > 8 * RES_MAXKB) return CARE_ESHAPE;
-      RAttn& A = L.att[a];
-      A.q_w = (const bf16_t*)sa.q_w; A.q_b = sa.q_b; A.o_w = (const bf16_t*)sa.o_w; A.o_b = sa.o_b; A.g = sa.ln_g; A.be = sa.ln_b;
-      A.kv = (const bf16_t*)sa.kv; A.kv_bs = sa.kv_batch_stride; A.nkeys = sa.nkeys; A.rows_per_kv = sa.rows_per_kv;
-      A.bias = sa.bias; A.bias_ld = sa.bias_ld;
-    }
-    L.w1 = (const bf16_t*)s.w1; L.b1 = s.b1; L.w2 = (const bf16_t*)s.w2; L.b2 = s.b2; L.fg = s.ffn_g; L.fbe = s.ffn_b;
-  }
-  p.n_layers = n_layers;
-  return 0;
-}
-
-}  // namespace
-extern std::atomic<int> care_res_dbg_prof, care_res_dbg_ghost;  // decode_resident.hip (care_decode_resident_debug)
-extern std::atomic<int> care_res_fenced_mode;                   // decode_resident.hip (care_resident_set_fenced): -1 auto, 0, 1
-namespace {
-
-// Which hand-off a resident launch on the current device takes: the fence-free one only where it was validated
-// (tests/test_gpu_resident.py's stress / contention tests run on gfx950 with all 256 CUs in one partition); any other
-// device, partition mode or an explicit care_resident_set_fenced(1) / CARE_RESIDENT_FENCED=1 gets the release / acquire
-// pair.  care_resident_set_fenced(0) forces the fence-free form (the validated arch is still a compile-time condition).
-inline int res_fenced_for_device() {
-  int mode = care_res_fenced_mode.load();
-  if (mode < 0) {
-    static const int env = [] { const char* e = getenv("CARE_RESIDENT_FENCED"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-    mode = env;
-  }
-  if (mode >= 0) return mode;
-  // decided once per device ordinal (hipGetDeviceProperties is a driver round trip in front of a latency-bound launch)
-  static std::atomic<int> per_device[64];
-  static const bool init = [] { for (auto& a : per_device) a.store(-1); return true; }();
-  (void)init;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 1;
-  if (dev >= 0 && dev < 64) {
-    const int known = per_device[dev].load(std::memory_order_relaxed);
-    if (known >= 0) return known;
-  }
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 1;
-  const bool gfx950 = strncmp(prop.gcnArchName, "gfx950", 6) == 0;
-  const int fenced = (gfx950 && prop.multiProcessorCount == 256) ? 0 : 1;
-  if (dev >= 0 && dev < 64) per_device[dev].store(fenced, std::memory_order_relaxed);
-  return fenced;
-}
-
-// Tuning / tool / test knobs of the resident launches: the environment is read ONCE per process (first launch), the
-// debug hooks are set through care_decode_resident_debug (tests, tools/resident_prof.py), never through the environment.
-struct ResKnobs {
-  int rb, small, half_rows, beam_cfg;  // -1: not set
-  ResKnobs() {
-    auto geti = [](const char* n) { const char* e = getenv(n); return e ? atoi(e) : -1; };
-    rb = geti("CARE_RESIDENT_RB"); small = geti("CARE_RESIDENT_SMALL"); half_rows = geti("CARE_RESIDENT_HALF_ROWS");
-    beam_cfg = geti("CARE_RESIDENT_BEAM_CFG");
-  }
-};
-inline const ResKnobs& res_knobs() {
-  static const ResKnobs k;
-  return k;
-}
-
-// Every workgroup of a resident launch must be resident at the same time: the grid is at most one workgroup per CU, and
-// the occupancy query must admit one workgroup of this kernel per CU (registers, LDS).  0 or a CARE_E* / hipError_t code.
-inline int res_check_residency(const void* kernel, int lds, int grid, int cus) {
-  int nb = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 256, (size_t)lds);
-  if (e != hipSuccess) return (int)e;
-  return (nb >= 1 && grid <= cus) ? 0 : CARE_ESHAPE;
 }
 
 }  // namespace

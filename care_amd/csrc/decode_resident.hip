@@ -32,6 +32,7 @@
 // caches and contexts, fp32 accumulators, LayerNorm and softmax statistics); sums run in another order, the same
 // order at every row count.
 #include "decode_resident.h"
+#include "decode_launch.h"
 
 namespace {
 
@@ -184,11 +185,7 @@ void care_decode_resident_debug(int prof_step, int ghost) {
 
 int64_t care_decode_resident_scratch(int rows, int d, int ff, int V) {
   if (rows < 1 || d < 1 || ff < 1 || V < 1) return CARE_EINVAL;
-  const int64_t R16 = (rows + 15) / 16 * 16;
-  int64_t parts = d == 512 ? (V + 63) / 64 : (V + 15) / 16;  // column items of the vocabulary phase (16 columns each when d_model > 512)
-  if (parts > 64 * RES_NP) parts = 64 * RES_NP;
-  // sync | xres, y, y2, q fp32 [R16, d] | ctx bf16 [R16, d] | h bf16 [R16, ff] | pmax, pidx, psum [R16, parts]
-  return RES_SYNC_BYTES + R16 * d * 4 * 4 + R16 * d * 2 + R16 * ff * 2 + R16 * parts * 12;
+  return res_layout(nullptr, nullptr, rows, d, ff, V, false);
 }
 
 int care_decode_resident(const care_resident_layer* layers, int n_layers, const float* word, const float* pos,
@@ -196,43 +193,19 @@ int care_decode_resident(const care_resident_layer* layers, int n_layers, const 
                          const void* vocab_w, int V, int d, int heads, int ff, int act, int rows, int T, int steps,
                          int bos, int eos, int pad, int32_t* fed, int fed_stride, float* score, int32_t* length,
                          int32_t* finished, void* scratch, int64_t scratch_bytes, int early_exit, int blocks, void* stream) {
-  if (!layers || !word || !pos || !emb_g || !emb_b || !vocab_w || !fed || !score || !length || !finished || !scratch)
-    return CARE_EINVAL;
-  if (n_layers < 1 || n_layers > RES_MAX_LAYERS || rows < 1 || T < 1 || steps < 1 || steps > T || V < 1 || fed_stride < T + 1)
-    return CARE_EINVAL;
+  const ResModel m{layers, n_layers, word, pos, sem, emb_g, emb_b, eps, vocab_w, V, d, heads, ff, act, T, fed_stride, scratch, scratch_bytes};
   const bool wide = d != 512;  // d_model 768 / 1024 with ff = 4 d_model, up to 128 rows (decode_resident_kernel's D)
-  if (heads * 64 != d || T > 8 * RES_MAXKB || V > 64 * 64 * RES_NP) return CARE_ESHAPE;
-  if (!wide && ff != 512 && ff != 1024 && ff != 2048) return CARE_ESHAPE;
-  if (wide && ((d != 768 && d != 1024) || ff != 4 * d || rows > 128)) return CARE_ESHAPE;
-  if (act < CARE_ACT_NONE || act > CARE_ACT_GELU) return CARE_EDTYPE;
-  if (scratch_bytes < care_decode_resident_scratch(rows, d, ff, V) || !care_aligned16(scratch)) return CARE_EINVAL;
+  if (const int rc = res_check(m, fed && score && length && finished, rows >= 1 && steps >= 1 && steps <= T,
+                               T <= 8 * RES_MAXKB && !(wide && rows > 128), care_decode_resident_scratch(rows, d, ff, V)))
+    return rc;
   RArgs p{};
-  if (const int rc = res_fill_layers(p, layers, n_layers)) return rc;
-  p.word = word; p.pos = pos; p.sem = sem; p.sem_div = sem_div > 0 ? sem_div : 1; p.emb_g = emb_g; p.emb_be = emb_b; p.eps = eps;
-  p.vocab = (const bf16_t*)vocab_w; p.V = V;
-  p.d = d; p.H = heads; p.ff = ff; p.act = act; p.R = rows; p.T = T; p.steps = steps; p.bos = bos; p.eos = eos; p.pad = pad; p.early = early_exit;
-  p.prof_step = care_res_dbg_prof.load();        // tools: phase clocks of that step -> scratch + 2048
-  p.ghost = care_res_dbg_ghost.load() ? 8 : 0;
-  p.fenced = res_fenced_for_device();   // tests: phases whose producers never all arrive (the watchdog)
+  if (const int rc = res_fill(p, m, sem_div > 0 ? sem_div : 1, rows, steps, bos, eos, pad, early_exit, true)) return rc;
   p.fed = fed; p.fed_stride = fed_stride; p.score = score; p.length = length; p.fin = finished;
+  res_layout(&p, (unsigned char*)scratch, rows, d, ff, V, false);
   const int64_t R16 = (rows + 15) / 16 * 16;
-  p.parts = wide ? ((V + 15) / 16 < 64 * RES_NP ? (V + 15) / 16 : 64 * RES_NP) : (V + 63) / 64;  // (the layout's stride; the launch's count below)
-  unsigned char* b = (unsigned char*)scratch;
-  p.sync = (unsigned*)b; b += RES_SYNC_BYTES;
-  p.xres = (float*)b; b += R16 * d * 4;
-  p.y = (float*)b; b += R16 * d * 4;
-  p.y2 = (float*)b; b += R16 * d * 4;
-  p.q = (float*)b; b += R16 * d * 4;
-  p.ctx = (bf16_t*)b; b += R16 * d * 2;
-  p.h = (bf16_t*)b; b += R16 * ff * 2;
-  p.pmax = (float*)b; b += R16 * p.parts * 4;
-  p.pidx = (int32_t*)b; b += R16 * p.parts * 4;
-  p.psum = (float*)b;
 
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return (int)e;
+  int cus = 0;
+  if (const int rc = res_device_cus(cus)) return rc;
   const ResKnobs& kn = res_knobs();
   // every workgroup must be resident (they wait for one another): at most one per CU; no more than the widest phase
   // has items (the vocabulary groups x row tiles, or a wave per (row, head))
@@ -251,47 +224,29 @@ int care_decode_resident(const care_resident_layer* layers, int n_layers, const 
   grid = (grid + 7) / 8 * 8;  // whole rounds over the 8 XCDs (PhaseMap)
   if (grid > cus) grid = cus;
   if (grid < RT) return CARE_ESHAPE;  // a workgroup per 16-row tile at least
-  {  // vocabulary partials per row = workgroups per row tile that have a column item (PhaseMap)
-    const int nper = ((grid & 7) == 0 && (grid >> 3) >= RG) ? 8 * ((grid >> 3) / RG) : grid / RG;
-    p.parts = nper < CIV ? nper : CIV;
-    if (p.parts > 64 * RES_NP) return CARE_ESHAPE;
-  }
+  p.parts = res_parts(grid, RG, CIV);  // (of this launch; the layout's stride is res_max_parts)
+  if (p.parts > 64 * RES_NP) return CARE_ESHAPE;
   const int kmax = wide ? (ff / 2 > d ? ff / 2 : d) : (ff > d ? ff : d);  // (wide: FFN dense2's tile holds a K half)
   int lds = 16 * (kmax + 8) * 2;
   if (rb * 16 * (512 + 8) * 2 > lds) lds = rb * 16 * (512 + 8) * 2;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 g(grid), blk(256);
-  int rc;
-  // (the residency check comes before anything is enqueued: a refused launch leaves the stream untouched)
-#define RES_LAUNCH(KCF, RB, SM, HF, SLOT) RES_LAUNCH_D(KCF, RB, SM, HF, 512, SLOT)
-#define RES_LAUNCH_D(KCF, RB, SM, HF, DM, SLOT)                                                                         \
-  do {                                                                                                                  \
-    const void* kfn = (const void*)decode_resident_kernel<KCF, RB, SM, HF, DM>;                                         \
-    if ((rc = care_allow_dynamic_lds(kfn, lds, g_res_lds_done[SLOT]))) return rc;                                        \
-    if (!g_res_ok[SLOT].load(std::memory_order_acquire)) {                                                              \
-      if ((rc = res_check_residency(kfn, lds, grid, cus))) return rc;                                                   \
-      g_res_ok[SLOT].store(1, std::memory_order_release);                                                               \
-    }                                                                                                                   \
-    if ((e = res_zero_words(p.sync, RES_SYNC_BYTES, st)) != hipSuccess) return (int)e;                               \
-    hipLaunchKernelGGL((decode_resident_kernel<KCF, RB, SM, HF, DM>), g, blk, lds, st, p);                              \
-  } while (0)
+#define RES_LAUNCH(SLOT, ...) /* an instance: its slot, then the kernel's template arguments */ \
+  return res_launch(decode_resident_kernel<__VA_ARGS__>, g_res_lds_done[SLOT], g_res_ok[SLOT], lds, grid, cus, p, st)
   // QKV / FFN dense1 in 16-column K-split items up to 64 rows (*measured* us / step with / without: 1 row 43.6 / 47.1,
   // 32 rows 60.7 / 65.0, 64 rows 66.0 / 67.7, 128 rows 76.9 / 77.5 with 8.1 against 4.6 us in FFN dense1); FFN dense2
   // over two workgroups per column tile up to 64 rows (ffn2_phase; *measured* ms per pass with / without: 1 row 1.28 / 1.33,
   // 16 rows 1.59 / 1.68, 32 rows 1.69 / 1.86, 64 rows 1.94 / 2.00)
   const bool small = kn.small >= 0 ? kn.small != 0 : rows <= 64;       // tuning (CARE_RESIDENT_SMALL)
   const bool half = rows <= (kn.half_rows >= 0 ? kn.half_rows : 64);   // tuning (CARE_RESIDENT_HALF_ROWS)
-  if (d == 768) RES_LAUNCH_D(6, 1, true, true, 768, 6);
-  else if (d == 1024) RES_LAUNCH_D(8, 1, true, true, 1024, 7);
-  else if (ff == 512) RES_LAUNCH(1, 1, true, false, 0);
-  else if (ff == 1024) RES_LAUNCH(2, 1, true, false, 1);
-  else if (rb == 2) RES_LAUNCH(4, 2, false, false, 3);
-  else if (small && half) RES_LAUNCH(4, 1, true, true, 5);
-  else if (small) RES_LAUNCH(4, 1, true, false, 4);
-  else RES_LAUNCH(4, 1, false, false, 2);
+  if (d == 768) RES_LAUNCH(6, 6, 1, true, true, 768);
+  else if (d == 1024) RES_LAUNCH(7, 8, 1, true, true, 1024);
+  else if (ff == 512) RES_LAUNCH(0, 1, 1, true, false);
+  else if (ff == 1024) RES_LAUNCH(1, 2, 1, true, false);
+  else if (rb == 2) RES_LAUNCH(3, 4, 2, false, false);
+  else if (small && half) RES_LAUNCH(5, 4, 1, true, true);
+  else if (small) RES_LAUNCH(4, 4, 1, true, false);
+  else RES_LAUNCH(2, 4, 1, false, false);
 #undef RES_LAUNCH
-#undef RES_LAUNCH_D
-  return care_launch_status();
 }
 
 }  // extern "C"

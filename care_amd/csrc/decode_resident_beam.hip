@@ -23,6 +23,7 @@
 //   the weight fragments (gemm_phase's RTB) - at 40 row tiles a workgroup per (row tile, column item) would stream every
 //   weight matrix 40 times through the L2s per step.
 #include "decode_beam_phase.h"
+#include "decode_launch.h"
 
 namespace {
 
@@ -152,12 +153,6 @@ constexpr int RES_BEAM_KERNELS = 10;
 std::atomic<unsigned long long> g_resb_lds_done[RES_BEAM_KERNELS];
 std::atomic<int> g_resb_ok[RES_BEAM_KERNELS];
 
-// parts (vocabulary partials per row) of a grid: workgroups per row group that have a column item (PhaseMap)
-inline int beam_parts(int grid, int RG, int CIV) {
-  const int nper = ((grid & 7) == 0 && (grid >> 3) >= RG) ? 8 * ((grid >> 3) / RG) : grid / RG;
-  return nper < CIV ? nper : CIV;
-}
-
 }  // namespace
 
 extern "C" {
@@ -181,12 +176,7 @@ int64_t care_decode_resident_beam_scratch(int clips, int beam, int d, int ff, in
 #if CARE_RES_BMK == 5
   if (beam > RES_BMK) return care_decode_resident_beam8_scratch(clips, beam, d, ff, V);
 #endif
-  const int64_t rows = (int64_t)clips * beam, R16 = (rows + 15) / 16 * 16;
-  int64_t parts = d == 512 ? (V + 63) / 64 : (V + 15) / 16;  // column items of the vocabulary phase (16 columns each when d_model > 512)
-  if (parts > 64 * RES_NP) parts = 64 * RES_NP;
-  // sync | xres, y, y2, q fp32 [R16, d] | ctx bf16 [R16, d] | h bf16 [R16, ff] | pmax, pidx, psum [R16, parts] |
-  // gval, ggid [R16, parts, RES_BMK] | hn bf16 [R16, d]
-  return RES_SYNC_BYTES + R16 * d * 4 * 4 + R16 * d * 2 + R16 * ff * 2 + R16 * parts * 12 + R16 * parts * RES_BMK * 8 + R16 * d * 2 * 2;  // (... | xa bf16 [R16, d])
+  return res_layout(nullptr, nullptr, (int64_t)clips * beam, d, ff, V, true);
 }
 
 int care_decode_resident_beam(const care_resident_layer* layers, int n_layers, const float* word, const float* pos,
@@ -195,64 +185,35 @@ int care_decode_resident_beam(const care_resident_layer* layers, int n_layers, c
                               int bos, int eos, int pad, int32_t* tok, int stride, int32_t* anc0, int32_t* anc1,
                               float* scores, int32_t* done, int32_t* nfin, float* fscore, int32_t* flen, int32_t* fhyp,
                               int fin_cap, void* scratch, int64_t scratch_bytes, int early_exit, int blocks, void* stream) {
-  if (!layers || !word || !pos || !emb_g || !emb_b || !vocab_w || !tok || !anc0 || !anc1 || !scores || !done || !nfin ||
-      !fscore || !flen || !fhyp || !scratch)
-    return CARE_EINVAL;
-  if (n_layers < 1 || n_layers > RES_MAX_LAYERS || clips < 1 || beam < 1 || need < 1 || fin_cap < 1 || T < 1 || steps < 1 ||
-      steps > T || V < 1 || stride < T + 1)
-    return CARE_EINVAL;
 #if CARE_RES_BMK == 5
   if (beam > RES_BMK && beam <= 8)
     return care_decode_resident_beam8(layers, n_layers, word, pos, sem, emb_g, emb_b, eps, vocab_w, V, d, heads, ff, act, clips, beam,
                                       need, T, steps, bos, eos, pad, tok, stride, anc0, anc1, scores, done, nfin, fscore, flen, fhyp,
                                       fin_cap, scratch, scratch_bytes, early_exit, blocks, stream);
 #endif
+  const ResModel m{layers, n_layers, word, pos, sem, emb_g, emb_b, eps, vocab_w, V, d, heads, ff, act, T, stride, scratch, scratch_bytes};
   // the advance phase keeps a hypothesis' positions one per lane (T + 1 <= 64), a clip's candidates one per lane
   // (beam^2 <= 64) and RES_BMK groups per row
-  const bool wide = d != 512;  // d_model 768 / 1024 with ff = 4 d_model, up to 128 rows (the kernel's D)
-  if (heads * 64 != d || T > 63 || V > 64 * 64 * RES_NP || beam > RES_BMK || V < 4 * RES_BMK * 4) return CARE_ESHAPE;
-  if (!wide && ff != 512 && ff != 1024 && ff != 2048) return CARE_ESHAPE;
-  if (wide && ((d != 768 && d != 1024) || ff != 4 * d || (int64_t)clips * beam > 256)) return CARE_ESHAPE;
-  if (act < CARE_ACT_NONE || act > CARE_ACT_GELU) return CARE_EDTYPE;
-  if (scratch_bytes < care_decode_resident_beam_scratch(clips, beam, d, ff, V) || !care_aligned16(scratch)) return CARE_EINVAL;
+  const bool wide = d != 512;  // d_model 768 / 1024 with ff = 4 d_model, up to 256 rows (the kernel's D)
+  if (const int rc = res_check(m, tok && anc0 && anc1 && scores && done && nfin && fscore && flen && fhyp,
+                               clips >= 1 && beam >= 1 && need >= 1 && fin_cap >= 1 && steps >= 1 && steps <= T,
+                               T <= 63 && beam <= RES_BMK && V >= 4 * RES_BMK * 4 && !(wide && (int64_t)clips * beam > 256),
+                               care_decode_resident_beam_scratch(clips, beam, d, ff, V)))
+    return rc;
   const int rows = clips * beam;
   RArgs p{};
-  if (const int rc = res_fill_layers(p, layers, n_layers)) return rc;
+  if (const int rc = res_fill(p, m, beam, rows, steps, bos, eos, pad, early_exit, true)) return rc;
   for (int l = 0; l < n_layers; ++l)
     for (int a = 0; a < p.L[l].n_att; ++a)
       if (p.L[l].att[a].rows_per_kv != beam) return CARE_EINVAL;  // the beams of a clip share its static keys (attn_shared_phase)
-  p.word = word; p.pos = pos; p.sem = sem; p.sem_div = beam; p.emb_g = emb_g; p.emb_be = emb_b; p.eps = eps;
-  p.vocab = (const bf16_t*)vocab_w; p.V = V;
-  p.d = d; p.H = heads; p.ff = ff; p.act = act; p.R = rows; p.T = T; p.steps = steps; p.bos = bos; p.eos = eos; p.pad = pad; p.early = early_exit;
-  p.prof_step = care_res_dbg_prof.load();
-  p.ghost = care_res_dbg_ghost.load() ? 8 : 0;
-  p.fenced = res_fenced_for_device();
   p.fed = tok; p.fed_stride = stride; p.score = scores; p.length = nullptr; p.fin = nullptr;
   p.bm = beam; p.nclips = clips; p.need = need; p.fin_cap = fin_cap;
   p.anc[0] = anc0; p.anc[1] = anc1; p.done = done; p.nfin = nfin; p.fscore = fscore; p.flen = flen; p.fhyp = fhyp;
-  const int64_t R16 = (rows + 15) / 16 * 16;
-  int64_t maxparts = wide ? (V + 15) / 16 : (V + 63) / 64;
-  if (maxparts > 64 * RES_NP) maxparts = 64 * RES_NP;
-  unsigned char* b = (unsigned char*)scratch;
-  p.sync = (unsigned*)b; b += RES_SYNC_BYTES;
-  p.xres = (float*)b; b += R16 * d * 4;
-  p.y = (float*)b; b += R16 * d * 4;
-  p.y2 = (float*)b; b += R16 * d * 4;
-  p.q = (float*)b; b += R16 * d * 4;
-  p.ctx = (bf16_t*)b; b += R16 * d * 2;
-  p.h = (bf16_t*)b; b += R16 * ff * 2;
-  p.pmax = (float*)b; b += R16 * maxparts * 4;
-  p.pidx = (int32_t*)b; b += R16 * maxparts * 4;
-  p.psum = (float*)b; b += R16 * maxparts * 4;
-  p.gval = (float*)b; b += R16 * maxparts * RES_BMK * 4;
-  p.ggid = (int32_t*)b; b += R16 * maxparts * RES_BMK * 4;
-  p.hn = (bf16_t*)b; b += R16 * d * 2;
-  p.xa = (bf16_t*)b;
+  res_layout(&p, (unsigned char*)scratch, rows, d, ff, V, true);
+  const int64_t R16 = (rows + 15) / 16 * 16, maxparts = res_max_parts(d, V);
 
-  int dev = 0, cus = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (e != hipSuccess) return (int)e;
+  int cus = 0;
+  if (const int rc = res_device_cus(cus)) return rc;
   // The forms by row count (CARE_RESIDENT_BEAM_CFG = 0 .. 3 forces one): up to 64 rows the K-split forms of the
   // greedy launch; up to 512 rows one row tile per workgroup (two in the vocabulary phase from 128 rows); beyond, several
   // row tiles per workgroup and weight fetch in every GEMM phase (2 / 2 / 2 / 4: form 3; 4 / 2 / 4 / 4: form 2).
@@ -281,41 +242,27 @@ int care_decode_resident_beam(const care_resident_layer* layers, int n_layers, c
   // ... a single row group (<= 16 rows at one tile per workgroup) takes every workgroup and the two-step fetch instead
   constexpr int LISTS = 64 * RES_MAXE / RES_BMK >= 48 ? 48 : 64 * RES_MAXE / RES_BMK / 8 * 8;   // (48 at 5 groups per list, 32 at 8)
   int vcap = RG == 1 ? grid : (LISTS * RG < grid ? LISTS * RG : grid);
-  while (vcap > 8 && beam_parts(vcap, RG, CIV) > maxparts) vcap -= 8;
+  while (vcap > 8 && res_parts(vcap, RG, CIV) > maxparts) vcap -= 8;
   p.vcap = vcap;
-  p.parts = beam_parts(vcap, RG, CIV);
+  p.parts = res_parts(vcap, RG, CIV);
   if (p.parts > maxparts || p.parts > 64 * RES_NP || p.parts < 1) return CARE_ESHAPE;
   const int kmax = wide ? (ff / 2 > d ? ff / 2 : d) : (ff > d ? ff : d);  // (wide: FFN dense2's tile holds a K half)
   int lds = 16 * (kmax + 8) * 2;
   const int rmax = rv > rq ? (rv > rf ? rv : rf) : (rq > rf ? rq : rf);
   if (rmax * 16 * (512 + 8) * 2 > lds) lds = rmax * 16 * (512 + 8) * 2;
   hipStream_t st = (hipStream_t)stream;
-  const dim3 g(grid), blk(256);
-  int rc;
-#define RESB_LAUNCH(KCF, RQ, RD, RF, RV, SM, KD, SLOT) RESB_LAUNCH_D(KCF, RQ, RD, RF, RV, SM, KD, 512, SLOT)
-#define RESB_LAUNCH_D(KCF, RQ, RD, RF, RV, SM, KD, DM, SLOT)                                                              \
-  do {                                                                                                                  \
-    const void* kfn = (const void*)decode_resident_beam_kernel<KCF, RQ, RD, RF, RV, SM, KD, DM>;                            \
-    if ((rc = care_allow_dynamic_lds(kfn, lds, g_resb_lds_done[SLOT]))) return rc;                                       \
-    if (!g_resb_ok[SLOT].load(std::memory_order_acquire)) {                                                             \
-      if ((rc = res_check_residency(kfn, lds, grid, cus))) return rc;                                                   \
-      g_resb_ok[SLOT].store(1, std::memory_order_release);                                                              \
-    }                                                                                                                   \
-    if ((e = res_zero_words(p.sync, RES_SYNC_BYTES, st)) != hipSuccess) return (int)e;                               \
-    hipLaunchKernelGGL((decode_resident_beam_kernel<KCF, RQ, RD, RF, RV, SM, KD, DM>), g, blk, lds, st, p);                 \
-  } while (0)
-  if (d == 768) RESB_LAUNCH_D(6, 1, 1, 1, 1, true, true, 768, 8);
-  else if (d == 1024) RESB_LAUNCH_D(8, 1, 1, 1, 1, true, true, 1024, 9);
-  else if (ff == 512) RESB_LAUNCH(1, 1, 1, 1, 1, true, true, 0);
-  else if (ff == 1024) RESB_LAUNCH(2, 1, 1, 1, 1, true, true, 1);
-  else if (cfg == 0) RESB_LAUNCH(4, 1, 1, 1, 1, true, true, 2);
-  else if (cfg == 1 && rv == 2) RESB_LAUNCH(4, 1, 1, 1, 2, false, true, 3);
-  else if (cfg == 1) RESB_LAUNCH(4, 1, 1, 1, 1, false, true, 4);
-  else if (cfg == 3) RESB_LAUNCH(4, 2, 2, 2, 4, false, false, 6);
-  else RESB_LAUNCH(4, 4, 2, 4, 4, false, false, 5);
+#define RESB_LAUNCH(SLOT, ...) /* an instance: its slot, then the kernel's template arguments */ \
+  return res_launch(decode_resident_beam_kernel<__VA_ARGS__>, g_resb_lds_done[SLOT], g_resb_ok[SLOT], lds, grid, cus, p, st)
+  if (d == 768) RESB_LAUNCH(8, 6, 1, 1, 1, 1, true, true, 768);
+  else if (d == 1024) RESB_LAUNCH(9, 8, 1, 1, 1, 1, true, true, 1024);
+  else if (ff == 512) RESB_LAUNCH(0, 1, 1, 1, 1, 1, true, true);
+  else if (ff == 1024) RESB_LAUNCH(1, 2, 1, 1, 1, 1, true, true);
+  else if (cfg == 0) RESB_LAUNCH(2, 4, 1, 1, 1, 1, true, true);
+  else if (cfg == 1 && rv == 2) RESB_LAUNCH(3, 4, 1, 1, 1, 2, false, true);
+  else if (cfg == 1) RESB_LAUNCH(4, 4, 1, 1, 1, 1, false, true);
+  else if (cfg == 3) RESB_LAUNCH(6, 4, 2, 2, 2, 4, false, false);
+  else RESB_LAUNCH(5, 4, 4, 2, 4, 4, false, false);
 #undef RESB_LAUNCH
-#undef RESB_LAUNCH_D
-  return care_launch_status();
 }
 
 }  // extern "C"

@@ -56,6 +56,25 @@ class ResidentMixin:
             L.ffn_g, L.ffn_b = ptr(w[ffn + "_g"]), ptr(w[ffn + "_be"])
         return layers
 
+    def _model_args(self, sem, d: int):
+        """The model arguments every decode call leads with, after (layers, n_layers): word .. act."""
+        w = self.w
+        return (ptr(w["word"]), ptr(w["pos"]), ptr(sem), ptr(w["emb_g"]), ptr(w["emb_be"]), self.eps, ptr(w["vocab"]), self.V, d,
+                self.H, self.ff, self.act)
+
+    def _beam_state(self, tag: str, B: int, bm: int, need: int):
+        """The beam state of csrc/beam.hip in the workspaces `tag`*."""
+        T, N, cap = self.T, B * bm, need + bm
+        return dict(tok=self.ws(tag + "tok", (N, T + 1), torch.int32),
+                    anc=[self.ws(tag + "anc%d" % i, (N, T + 1), torch.int32) for i in range(2)],
+                    scores=self.ws(tag + "scores", (N,)), done=self.ws(tag + "done", (B,), torch.int32),
+                    **dict(zip(("nfin", "fscore", "flen", "fhyp"), self.ws_block(tag + "out", self._beam_out_parts(B, cap)))))
+
+    def _beam_state_args(self, v, cap: int, scratch, nbytes: int):
+        """The tail of the beam calls: tok, stride, anc0, anc1, scores .. fhyp, cap, scratch, bytes."""
+        return (ptr(v["tok"]), self.T + 1, ptr(v["anc"][0]), ptr(v["anc"][1]),
+                *(ptr(v[k]) for k in ("scores", "done", "nfin", "fscore", "flen", "fhyp")), cap, ptr(scratch), nbytes)
+
     def beam_resident(self, mem: torch.Tensor, sem: Optional[torch.Tensor], bm: int, need: int,
                       sem_embs: Optional[torch.Tensor] = None, early_exit: bool = True):
         """Beam search of B clips x bm beams in ONE launch (care_decode_resident_beam): the step loop of
@@ -63,32 +82,19 @@ class ResidentMixin:
         device, stopping once every clip is done (Translator.py:77-81).  Returns the per-clip results of engine.beam:
         nfin [B], fscore / flen [B, need + bm], fhyp [B, need + bm, T + 1]; no host synchronisation here."""
         B, Lk, d = mem.shape
-        T, w, N, cap = self.T, self.w, mem.shape[0] * bm, need + bm
+        T, N, cap = self.T, mem.shape[0] * bm, need + bm
         sem = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
         ckv = self.cross_kv(mem, tag="rb_ckv", resident=True)
         akv = self.attr_kv(sem_embs, tag="rb_akv") if self.attr_att else None
-        tok = self.ws("rb_tok", (N, T + 1), torch.int32)
-        anc = [self.ws("rb_anc%d" % i, (N, T + 1), torch.int32) for i in range(2)]
-        scores, done = self.ws("rb_scores", (N,)), self.ws("rb_done", (B,), torch.int32)
-        nfin, fscore, flen, fhyp = self.ws_block("rb_out", self._beam_out_parts(B, cap))
+        v = self._beam_state("rb_", B, bm, need)
         layers = self._resident_layers("rb_", N, bm, ckv, akv, Lk)
         nbytes = self.lib.care_decode_resident_beam_scratch(B, bm, d, self.ff, self.V)
         scratch = self.ws("rb_scratch", (nbytes,), torch.uint8)
-        self.call("care_decode_resident_beam", ctypes.addressof(layers), self.n_layers, ptr(w["word"]), ptr(w["pos"]), ptr(sem),
-             ptr(w["emb_g"]), ptr(w["emb_be"]), self.eps, ptr(w["vocab"]), self.V, d, self.H, self.ff, self.act, B, bm, need, T, T,
-             BOS, EOS, PAD, ptr(tok), T + 1, ptr(anc[0]), ptr(anc[1]), ptr(scores), ptr(done), ptr(nfin), ptr(fscore), ptr(flen),
-             ptr(fhyp), cap, ptr(scratch), nbytes, int(bool(early_exit)), 0, tag="decode_resident_beam")
+        self.call("care_decode_resident_beam", ctypes.addressof(layers), self.n_layers, *self._model_args(sem, d), B, bm, need, T, T,
+                  BOS, EOS, PAD, *self._beam_state_args(v, cap, scratch, nbytes), int(bool(early_exit)), 0, tag="decode_resident_beam")
         self.last_decode = dict(clips=B, steps=scratch[8:12].view(torch.int32)[0], compactions=0, resident=True,
                                 row_steps=None)
-        return nfin, fscore, flen, fhyp
-
-    def _chain_state(self, B: int, bm: int, need: int):
-        T, N, cap = self.T, B * bm, need + bm
-        return dict(tok=self.ws("cb_tok", (N, T + 1), torch.int32),
-                    anc=[self.ws("cb_anc%d" % i, (N, T + 1), torch.int32) for i in range(2)],
-                    scores=self.ws("cb_scores", (N,)), done=self.ws("cb_done", (B,), torch.int32),
-                    **dict(zip(("nfin", "fscore", "flen", "fhyp"), self.ws_block("cb_out", self._beam_out_parts(B, cap)))),
-                    idx=self.ws("cb_idx", (B,), torch.int32), cnt=self.ws("cb_cnt", (1,), torch.int32))
+        return v["nfin"], v["fscore"], v["flen"], v["fhyp"]
 
     def beam_chain_steps(self, mem: torch.Tensor, sem: Optional[torch.Tensor], bm: int, need: int, t0: int, t1: int,
                          sem_embs: Optional[torch.Tensor] = None, count_live: bool = True):
@@ -98,21 +104,20 @@ class ResidentMixin:
         state.  Ends with the partition of the clips by `done` (care_active_slots: cb_cnt = clips still live).  No host
         synchronisation here."""
         B, Lk, d = mem.shape
-        T, w, N, cap = self.T, self.w, mem.shape[0] * bm, need + bm
+        T, N, cap = self.T, mem.shape[0] * bm, need + bm
         sem = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
         kvs = self.__dict__.setdefault("_chain_kv", {})
         if t0 == 1:  # (static workspaces: the handles of a (clips, beam) stay valid for the later segments' graphs)
             kvs[(B, bm)] = (self.cross_kv(mem, tag="cb_ckv", resident=True),
                             self.attr_kv(sem_embs, tag="cb_akv") if self.attr_att else None)
         ckv, akv = kvs[(B, bm)]
-        v = self._chain_state(B, bm, need)
+        v = self._beam_state("cb_", B, bm, need)
+        v.update(idx=self.ws("cb_idx", (B,), torch.int32), cnt=self.ws("cb_cnt", (1,), torch.int32))
         layers = self._resident_layers("cb_", N, bm, ckv, akv, Lk)
         nbytes = self.lib.care_decode_chain_beam_scratch(B, bm, d, self.ff, self.V)
         scratch = self.ws("cb_scratch", (nbytes,), torch.uint8)
-        self.call("care_decode_chain_beam", ctypes.addressof(layers), self.n_layers, ptr(w["word"]), ptr(w["pos"]), ptr(sem),
-                  ptr(w["emb_g"]), ptr(w["emb_be"]), self.eps, ptr(w["vocab"]), self.V, d, self.H, self.ff, self.act, B, bm, need, T,
-                  t0, t1, BOS, EOS, PAD, ptr(v["tok"]), T + 1, ptr(v["anc"][0]), ptr(v["anc"][1]), ptr(v["scores"]), ptr(v["done"]),
-                  ptr(v["nfin"]), ptr(v["fscore"]), ptr(v["flen"]), ptr(v["fhyp"]), cap, ptr(scratch), nbytes,
+        self.call("care_decode_chain_beam", ctypes.addressof(layers), self.n_layers, *self._model_args(sem, d), B, bm, need, T,
+                  t0, t1, BOS, EOS, PAD, *self._beam_state_args(v, cap, scratch, nbytes),
                   int(os.environ.get("CARE_CHAIN_FORM", "-1")), tag="decode_chain_beam")
         if count_live:
             self.call("care_active_slots", ptr(v["done"]), B, ptr(v["idx"]), ptr(v["cnt"]))
@@ -160,7 +165,7 @@ class ResidentMixin:
         every clip has ended (Translator.py:77-81).  Returns device tensors fed int32 [B, T + 1], length int32 [B],
         score fp32 [B]; `self.last_decode["steps"]` is a 0-dim DEVICE tensor (no host synchronisation here)."""
         B, Lk, d = mem.shape
-        T, w = self.T, self.w
+        T = self.T
         steps = T if steps is None else steps
         sem = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
         ckv = self.cross_kv(mem, tag="r_ckv", resident=True)
@@ -170,9 +175,9 @@ class ResidentMixin:
         layers = self._resident_layers("r_", B, 1, ckv, akv, Lk)
         nbytes = self.lib.care_decode_resident_scratch(B, d, self.ff, self.V)
         scratch = self.ws("r_scratch", (nbytes,), torch.uint8)
-        self.call("care_decode_resident", ctypes.addressof(layers), self.n_layers, ptr(w["word"]), ptr(w["pos"]), ptr(sem), 1,
-             ptr(w["emb_g"]), ptr(w["emb_be"]), self.eps, ptr(w["vocab"]), self.V, d, self.H, self.ff, self.act, B, T, steps,
-             BOS, EOS, PAD, ptr(fed), T + 1, ptr(score), ptr(length), ptr(fin), ptr(scratch), nbytes,
-             int(bool(early_exit)), 0, tag="decode_resident")
+        model = self._model_args(sem, d)
+        self.call("care_decode_resident", ctypes.addressof(layers), self.n_layers, *model[:3], 1, *model[3:], B, T, steps,
+                  BOS, EOS, PAD, ptr(fed), T + 1, ptr(score), ptr(length), ptr(fin), ptr(scratch), nbytes,
+                  int(bool(early_exit)), 0, tag="decode_resident")
         self.last_decode = dict(clips=B, steps=scratch[8:12].view(torch.int32)[0], compactions=0, resident=True)
         return fed, length, score

@@ -175,6 +175,161 @@ def test_abi_library_exports_every_declared_symbol():
     assert loaded.care_argmax_parts_bf16_min(32768, 10547, 512, 0, 8) == 8    # fp32 rows stay on the 128-row kernel
 
 
+def _resident_host_golden():
+    import json
+    return json.load(open(os.path.join(ROOT, "tests", "golden", "resident_host_abi.json")))
+
+
+SCRATCH_GRID = dict(rows=(0, 1, 3, 16, 17, 128, 256), beam=(1, 2, 5, 6, 8), V=(80, 500, 10547, 16384, 20000),
+                    d_ff=((512, 512), (512, 1024), (512, 2048), (768, 3072), (1024, 4096)))
+
+
+def resident_scratch_sizes(lib):
+    """The three *_scratch entry points over SCRATCH_GRID, in one fixed order (also what recorded the fixture)."""
+    g = SCRATCH_GRID
+    shapes = [(d, ff, V) for d, ff in g["d_ff"] for V in g["V"]]
+    out = {"care_decode_resident_scratch": [lib.care_decode_resident_scratch(r, *s) for r in g["rows"] for s in shapes]}
+    for name in ("care_decode_resident_beam_scratch", "care_decode_chain_beam_scratch"):
+        out[name] = [getattr(lib, name)(c, b, *s) for c in g["rows"] for b in g["beam"] for s in shapes]
+    return out
+
+
+def test_resident_scratch_sizes_are_the_recorded_ones():
+    """The workspace sizes of the resident / chained decodes (csrc/decode_launch.h: res_layout) over rows x beam x model x
+    vocabulary, against the values recorded from the library of the commit the fixture names.  V = 20000: `parts` is
+    capped, not rejected; beams 6 and 8: the second instance's 8 groups per list."""
+    from care_amd import _lib, build
+
+    build.build_all()
+    want = _resident_host_golden()["scratch"]
+    assert _resident_host_golden()["scratch_grid"] == {k: [list(v) if k == "d_ff" else v for v in vs] for k, vs in SCRATCH_GRID.items()}
+    for variant in build.VARIANTS:
+        got = resident_scratch_sizes(_lib.load(variant=variant))
+        assert set(got) == set(want)
+        for name in want:
+            assert len(want[name]) == len(got[name]) >= 7 * 25 and got[name] == want[name], (variant, name)
+
+
+def resident_malformed_calls(lib):
+    """{entry point: {case: argument list}}: ONE valid call per entry point (dummy non-null pointers: nothing but `layers`
+    is read before the checks pass) and malformed variants of it, each rejected before the library asks for a device."""
+    import ctypes
+
+    from care_amd import _lib
+
+    PTR, BIG = 0x10000, 1 << 40
+    keep = []  # the ctypes layer arrays must outlive the calls
+
+    def layers(rows_per_kv, edit=None):
+        arr = (_lib.ResidentLayer * 1)()
+        L = arr[0]
+        for f, t in _lib.ResidentLayer._fields_:
+            if t is _lib.c_void_p:
+                setattr(L, f, PTR)
+        L.n_att = 2
+        for A in L.att:
+            for f, t in _lib.ResidentAttn._fields_:
+                if t is _lib.c_void_p:
+                    setattr(A, f, PTR)
+            A.kv_batch_stride, A.nkeys, A.rows_per_kv, A.bias_ld = 16 * 1024, 16, rows_per_kv, 16
+        if edit:
+            edit(L)
+        keep.append(arr)
+        return ctypes.addressof(arr)
+
+    model = dict(word=PTR, pos=PTR, sem=PTR, emb_g=PTR, emb_b=PTR, eps=1e-5, vocab_w=PTR, V=10547, d=512, heads=8, ff=2048, act=1)
+    state = dict(tok=PTR, stride=31, anc0=PTR, anc1=PTR, scores=PTR, done=PTR, nfin=PTR, fscore=PTR, flen=PTR, fhyp=PTR, fin_cap=10,
+                 scratch=PTR, scratch_bytes=BIG)
+    valid = {
+        "care_decode_resident": dict(layers=None, n_layers=1, **{k: model[k] for k in ("word", "pos", "sem")}, sem_div=1,
+                                     **{k: v for k, v in model.items() if k not in ("word", "pos", "sem")}, rows=4, T=30, steps=30,
+                                     bos=1, eos=2, pad=0, fed=PTR, stride=31, score=PTR, length=PTR, finished=PTR, scratch=PTR,
+                                     scratch_bytes=BIG, early_exit=1, blocks=0, stream=None),
+        "care_decode_resident_beam": dict(layers=None, n_layers=1, **model, clips=3, beam=5, need=5, T=30, steps=30, bos=1, eos=2,
+                                          pad=0, **state, early_exit=1, blocks=0, stream=None),
+        "care_decode_chain_beam": dict(layers=None, n_layers=1, **model, clips=3, beam=5, need=5, T=30, t0=1, t1=30, bos=1, eos=2,
+                                       pad=0, **state, form=-1, stream=None),
+    }
+
+    def null(field):
+        return lambda L: setattr(L, field, None)
+
+    def att(**kw):
+        return lambda L: [setattr(L.att[1], k, v) for k, v in kw.items()]
+
+    wide = dict(d=768, heads=12, ff=3072)
+    common = {  # case: (argument overrides, edit of the layer)
+        "null model pointer": (dict(word=None), None), "null scratch": (dict(scratch=None), None),
+        "n_layers 0": (dict(n_layers=0), None), "n_layers 5": (dict(n_layers=5), None),
+        "stride T": (dict(stride=30), None), "heads * 64 != d": (dict(heads=7), None), "ff 768": (dict(ff=768), None),
+        "wide, ff != 4 d": (dict(wide, ff=2048), None), "act -1": (dict(act=-1), None), "act 99": (dict(act=99), None),
+        "scratch too small": (dict(scratch_bytes="need - 1"), None), "scratch unaligned": (dict(scratch=PTR + 8), None),
+        "layer: null w1": ({}, null("w1")), "layer: null attention kv": ({}, lambda L: setattr(L.att[0], "kv", None)),
+        "layer: n_att 3": ({}, lambda L: setattr(L, "n_att", 3)), "layer: nkeys 0": ({}, att(nkeys=0)),
+        "layer: nkeys 129": ({}, att(nkeys=129)),
+        # two rules of different codes at once: which one answers
+        "null pointer + act": (dict(pos=None, act=99), None), "n_layers 5 + heads": (dict(n_layers=5, heads=7), None),
+        "heads + act": (dict(heads=7, act=99), None), "act + scratch too small": (dict(act=99, scratch_bytes="need - 1"), None),
+        "ff + scratch unaligned": (dict(ff=768, scratch=PTR + 8), None),
+        "scratch too small + nkeys 0": (dict(scratch_bytes="need - 1"), att(nkeys=0)),
+        "wide, ff != 4 d + null w1": (dict(wide, ff=2048), null("w1")),
+    }
+    beam_common = {
+        "null state pointer": (dict(anc1=None), None), "rows_per_kv != beam": ({}, att(rows_per_kv=1)), "beam 9": (dict(beam=9), None),
+        "T 64": (dict(T=64, stride=65), None), "V 79": (dict(V=79), None), "need 0": (dict(need=0), None),
+        "nkeys 129 + rows_per_kv": ({}, att(nkeys=129, rows_per_kv=1)), "beam 9 + act": (dict(beam=9, act=99), None),
+    }
+    own = {
+        "care_decode_resident": {
+            "null state pointer": (dict(length=None), None), "steps > T": (dict(steps=31), None), "rows 0": (dict(rows=0), None),
+            "T 129": (dict(T=129, steps=129, stride=130), None), "wide, 129 rows": (dict(wide, rows=129), None),
+            "wide, 129 rows + act": (dict(wide, rows=129, act=99), None), "steps > T + T 129": (dict(T=129, steps=130, stride=130), None),
+        },
+        "care_decode_resident_beam": dict(beam_common, **{
+            "steps > T": (dict(steps=31), None), "wide, 260 rows": (dict(wide, clips=52), None),
+            "wide, 260 rows + act": (dict(wide, clips=52, act=99), None), "steps > T + V 79": (dict(steps=31, V=79), None),
+            "beam 8: V 127": (dict(beam=8, V=127), att(rows_per_kv=8)), "beam 8: rows_per_kv 5": (dict(beam=8), att(rows_per_kv=5)),
+        }),
+        "care_decode_chain_beam": dict(beam_common, **{
+            "d 768": (dict(wide), None), "t0 0": (dict(t0=0), None), "t1 < t0": (dict(t0=5, t1=4), None), "t1 > T": (dict(t1=31), None),
+            "beam 6": (dict(beam=6), None), "rows > 2^20 + null w1": (dict(clips=300000), null("w1")),
+            "scratch too small + rows > 2^20": (dict(clips=300000, scratch_bytes="need - 1"), None), "t0 0 + d 768": (dict(wide, t0=0), None),
+        }),
+    }
+    calls = {}
+    for name, base in valid.items():
+        calls[name] = {}
+        for case, (over, edit) in dict(common, **own[name]).items():
+            a = dict(base, **over)
+            assert set(a) == set(base), (name, case)
+            a["layers"] = layers(a.get("beam", 1), edit)
+            if a["scratch_bytes"] == "need - 1":
+                rows = (a["rows"],) if "rows" in a else (a["clips"], a["beam"])
+                a["scratch_bytes"] = getattr(lib, name + "_scratch")(*rows, a["d"], a["ff"], a["V"]) - 1
+            calls[name][case] = list(a.values())
+    return calls, keep
+
+
+def test_resident_entry_points_reject_malformed_calls_with_the_recorded_codes():
+    """Which CARE_E* code a malformed call of care_decode_resident / _resident_beam / _chain_beam gets - calls that break
+    two rules of different codes included: the order of the checks (csrc/decode_launch.h: res_check, res_fill) - against
+    the codes recorded from the library of the commit the fixture names.  Every case is rejected before the library asks
+    for a device (a code of -1 .. -4, never a hipError_t), so a machine with a GPU and one without see the same."""
+    from care_amd import _lib, build
+
+    build.build_all()
+    want = _resident_host_golden()["rejections"]
+    for variant in build.VARIANTS:
+        lib = _lib.load(variant=variant)
+        calls, keep = resident_malformed_calls(lib)
+        assert set(calls) == set(want)
+        for name, cases in calls.items():
+            assert set(cases) == set(want[name]) and len(cases) >= 15
+            assert all(-4 <= code <= -1 for code in want[name].values())
+            got = {case: getattr(lib, name)(*args) for case, args in cases.items()}
+            assert got == want[name], (variant, name, {c: (got[c], want[name][c]) for c in got if got[c] != want[name][c]})
+
+
 def test_synth_generator_is_deterministic_and_portable():
     from care_amd.synth import synth_state_dict, tensor_sha256, uniform
 
