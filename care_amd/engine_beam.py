@@ -82,25 +82,34 @@ class BeamMixin:
                 self.call("care_beam_select", ptr(s[lo:hi]), s.stride(0), V, bm, ptr(cval[lo:hi]),
                      ptr(cidx[lo:hi]), hi - lo, 4 if self.plan.small_beam else 1, tag="step_beam_select")
 
-    # ------------------------------------------------------------------ beam search with early exit + compaction
+    # ------------------------------------------------------------------ the step loop; early exit + compaction
+    def _beam_init(self, v, rows):
+        """The beam state before step 1: every hypothesis EOS after its BOS, every ancestor the row itself (`rows`: the
+        row numbers), scores and finished lists zero."""
+        v["tok"].fill_(EOS); v["tok"][:, 0] = BOS
+        for a in v["anc"]:
+            a.copy_(rows.unsqueeze(1).expand(a.shape))
+        for k in ("scores", "done", "nfin", "fscore", "flen", "fhyp"):
+            v[k].zero_()
+
+    def _beam_advance(self, v, t, bm, need, cval, cidx):
+        """Beam.advance of step t (misc/Decoding/Beam.py:45-85) on the candidates cval / cidx of every row."""
+        a_old, a_new = v["anc"][(t - 1) & 1], v["anc"][t & 1]
+        self.call("care_beam_advance", ptr(cval), ptr(cidx), ptr(v["scores"]), bm, ptr(v["tok"]), ptr(a_old), ptr(a_new),
+             ptr(v["done"]), ptr(v["nfin"]), need + bm, ptr(v["fscore"]), ptr(v["flen"]), ptr(v["fhyp"]), t, self.T, need, EOS,
+             self.V, self.T + 1, v["n"])
+
     def _beam_steps(self, v, t0, t1, bm, need):
-        """Steps t0 .. t1 of the beam search on the n clips (n * bm rows) of state `v`; ends with the
-        partition of the clip slots (care_active_slots on `done`)."""
-        n, T, d = v["n"], self.T, self.d
-        N, cap = n * bm, need + bm
-        B = v["B"]
-        self._ws_cap = [(n, B), (N, B * bm)]
-        tag = v["tag"]
+        """Steps t0 .. t1 of the beam search on the n clips (n * bm rows) of state `v` (tok, anc, scores, done, nfin, fscore,
+        flen, fhyp, sem, ckv, akv, skv, Lk, tag, n)."""
+        tag, N = v["tag"], v["n"] * bm
         cval, cidx = self.ws(tag + "cval", (N, bm)), self.ws(tag + "cidx", (N, bm), torch.int32)
         sel = self._beam_select_ws(tag, N)  # one form for the whole pass, whatever the compaction leaves
         for t in range(t0, t1 + 1):
-            a_old, a_new = v["anc"][(t - 1) & 1], v["anc"][t & 1]
-            x, xb = self._decode_step(t, N, bm, v["tok"], a_old, v["sem"], v["ckv"], v["skv"], self.Lk, tag, akv=v["akv"])
+            x, xb = self._decode_step(t, N, bm, v["tok"], v["anc"][(t - 1) & 1], v["sem"], v["ckv"], v["skv"], v["Lk"], tag,
+                                      akv=v["akv"])
             self._beam_select(tag, sel, x, xb, N, bm, cval, cidx)
-            self.call("care_beam_advance", ptr(cval), ptr(cidx), ptr(v["scores"]), bm, ptr(v["tok"]), ptr(a_old), ptr(a_new),
-                 ptr(v["done"]), ptr(v["nfin"]), cap, ptr(v["fscore"]), ptr(v["flen"]), ptr(v["fhyp"]), t, T, need, EOS,
-                 self.V, T + 1, n)
-        self.call("care_active_slots", ptr(v["done"]), n, ptr(v["idx"]), ptr(v["cnt"]))
+            self._beam_advance(v, t, bm, need, cval, cidx)
 
     def beam_early_exit(self, feats: List[torch.Tensor], bm: int, need: int, lean: bool = False, use_graph: bool = True,
                         plan: Optional[forms.PassPlan] = None):
@@ -122,7 +131,7 @@ class BeamMixin:
             N = n * bm
             self._ws_cap = [(n, B), (N, B * bm)]
             tag = "b%d_" % par
-            return dict(tag=tag, n=n, B=B, idx=idx, cnt=cnt,
+            return dict(tag=tag, n=n, B=B, Lk=self.Lk,
                         tok=self.ws(tag + "tok", (N, T + 1), torch.int32),
                         anc=[self.ws(tag + "anc%d" % i, (N, T + 1), torch.int32) for i in range(2)],
                         scores=self.ws(tag + "scores", (N,)),
@@ -131,27 +140,25 @@ class BeamMixin:
                         fscore=self.ws(tag + "fscore", (n, cap)), flen=self.ws(tag + "flen", (n, cap), torch.int32),
                         fhyp=self.ws(tag + "fhyp", (n, cap, T + 1), torch.int32), clip=self.ws(tag + "clip", (n,), torch.int32))
 
+        def run_steps(v, t0, t1):
+            """... and the partition of the clip slots by `done`"""
+            self._ws_cap = [(v["n"], B), (v["n"] * bm, B * bm)]
+            self._beam_steps(v, t0, t1, bm, need)
+            self.call("care_active_slots", ptr(v["done"]), v["n"], ptr(idx), ptr(cnt))
+
         def first_segment():
             self._ws_cap = None
             enc = self.encode(feats, plan.lean, static=True, small=plan.small)
             mem, sem = enc["encoder_hidden_states"], enc.get("semantic_hidden_states")
             v = state(0, B)
-            N = B * bm
-            v["tok"].fill_(EOS); v["tok"][:, 0] = BOS
-            rows = self._arange(N)
-            for a in v["anc"]:
-                a.copy_(rows.unsqueeze(1).expand(N, T + 1))
-            for k in ("scores", "done", "nfin", "fscore", "flen", "fhyp"):
-                v[k].zero_()
+            self._beam_init(v, self._arange(B * bm))
             torch.add(self._arange(B), 0, out=v["clip"])   # (an elementwise kernel, not a memcpy node in the captured graph: see csrc/decode_resident.h, res_zero_kernel)
             v["sem"] = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
             self._ws_cap = None
-            v["ckv"] = self.cross_src(mem, N)
+            v["ckv"] = self.cross_src(mem, B * bm)
             v["akv"] = self.attr_kv(enc.get("semantic_embs")) if self.attr_att else None
-            self._beam_steps(v, 1, min(S, T), bm, need)
+            run_steps(v, 1, min(S, T))
             return enc, v
-
-        replayable = lambda key, fn: self._replay(key, fn, use_graph)
 
         def flush(v):
             """finished lists of every slot of v -> the per-clip outputs"""
@@ -161,30 +168,14 @@ class BeamMixin:
                 self._call_rows("care_scatter_rows", v[k], out[k], v["clip"], n)
             self._call_rows("care_scatter_rows", v["fhyp"].view(n, -1), out["fhyp"].view(B, -1), v["clip"], n)
 
-        try:
-            enc, v = replayable(forms.graph_key("bseg0", plan, feats, S), first_segment)
-            par, t = 0, min(S, T) + 1
-            stats = dict(clips=B, steps=t - 1, row_steps=B * bm * (t - 1), compactions=0)
-            self.last_decode = stats
-            while True:
-                active = self._host_count(cnt)
-                if active == 0 or t > T:
-                    break
-                m = self._slot_bucket(active, B)
-                if m * 4 <= v["n"] * 3 and v["n"] * bm >= 2048:
-                    flush(v)
-                    v = self._compact_beam(v, state(par ^ 1, m), idx, active, bm)
-                    par ^= 1
-                    stats["compactions"] += 1
-                t1 = min(t + S - 1, T)
-                vv = v
-                replayable(("bseg", plan, t, t1, v["n"], par), lambda: self._beam_steps(vv, t, t1, bm, need))
-                stats["steps"] = t1
-                stats["row_steps"] += v["n"] * bm * (t1 - t + 1)
-                t = t1 + 1
+        def compact(v, par, m, active):
             flush(v)
-        finally:
-            self._ws_cap = None
+            return self._compact_beam(v, state(par, m), idx, active, bm)
+
+        enc, v = self._segments(B, bm, S, forms.graph_key("bseg0", plan, feats, S), first_segment,
+                                lambda t, t1, n, par: ("bseg", plan, t, t1, n, par), run_steps, use_graph, cnt=cnt,
+                                count_last=True, compact=compact)
+        flush(v)
         return enc, out["nfin"], out["fscore"], out["flen"], out["fhyp"]
 
     def _compact_beam(self, v, w, idx, active, bm):
@@ -211,23 +202,7 @@ class BeamMixin:
             self.call("care_remap_rows", ptr(b), b.numel(), ptr(cmap), bm)
         for a, b in zip(v["skv"], w["skv"]):
             self._call_rows("care_gather_rows", a, b, idx_r, M)
-
-        def moved(name, src, per=1):
-            if src is None:
-                return None
-            s2 = src.view(n, -1)
-            dst = self.ws(tag + name, (m, s2.shape[1]), src.dtype)
-            self._call_rows("care_gather_rows", s2, dst, idx, m)
-            return dst.view((m * per,) + tuple(src.shape[1:])) if per > 1 else dst.view((m,) + tuple(src.shape[1:]))
-
-        w["sem"] = moved("sem", v["sem"])
-        if isinstance(v["ckv"], tuple):
-            w["ckv"] = (moved("mem", v["ckv"][0]),) * len(v["ckv"])
-        else:
-            w["ckv"] = [moved("ckv%d" % i, kv, self.Lk) for i, kv in enumerate(v["ckv"])]
-        w["akv"] = [moved("akv%d" % i, kv, self.topk) for i, kv in enumerate(v["akv"])] if v["akv"] is not None else None
-        w["clip"][active:].fill_(-1)
-        return w
+        return self._move_clips(v, w, idx, active)
 
     def translate_beam(self, feats: List[torch.Tensor], bm: int, need: int, use_graph: bool = True, lean: bool = False,
                        early_exit: Optional[bool] = None):
@@ -305,23 +280,13 @@ class BeamMixin:
         T, N = self.T, mem.shape[0] * bm
         mem = mem.to(self.device, mem.dtype if mem.dtype == self.h16 else torch.float32)  # bf16: lean encode
         sem = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
-        cap = need + bm
-        tok = self.ws("b_tok", (N, T + 1), torch.int32)
-        anc = [self.ws("b_anc%d" % i, (N, T + 1), torch.int32) for i in range(2)]
-        tok.fill_(EOS); tok[:, 0] = BOS
-        rows = torch.arange(N, device=self.device, dtype=torch.int32)
-        for a in anc:
-            a.copy_(rows.unsqueeze(1).expand(N, T + 1))
-        scores = self.ws("b_scores", (N,)); scores.zero_()
-        done = self.ws("b_done", (B,), torch.int32); done.zero_()
-        nfin, fscore, flen, fhyp = self.ws_block("b_out", self._beam_out_parts(B, cap))
-        nfin.zero_(); fscore.zero_(); flen.zero_(); fhyp.zero_()
-        cval = self.ws("b_cval", (N, bm))
-        cidx = self.ws("b_cidx", (N, bm), torch.int32)
-        vpad = (self.V + 63) // 64 * 64  # 16-byte aligned row stride -> the GEMM's vector store path
+        v = dict(self._beam_state("b_", B, bm, need), tag="b_", n=B, Lk=Lk, sem=sem)
+        self._beam_init(v, torch.arange(N, device=self.device, dtype=torch.int32))
         if others:
             # model ensembling: every member steps on the shared prefixes (tok / ancestors) with state of its own, its
             # vocabulary logits in memory; the averaged log-probabilities' top bm -> the one state machine
+            cval, cidx = self.ws("b_cval", (N, bm)), self.ws("b_cidx", (N, bm), torch.int32)
+            vpad = (self.V + 63) // 64 * 64  # 16-byte aligned row stride -> the GEMM's vector store path
             per = []
             for e, m, s_, se in [(self, mem, sem, sem_embs)] + list(others):
                 m = m.to(e.device, m.dtype if m.dtype == e.h16 else torch.float32)
@@ -329,26 +294,18 @@ class BeamMixin:
                 per.append(dict(e=e, sem=s_, ckv=e.cross_src(m, N), akv=e.attr_kv(se) if e.attr_att else None, Lk=m.shape[1],
                                 skv=[e.ws("b_skv%d" % li, (N, T, 2 * e.d), e.wt) for li in range(e.n_layers)],
                                 logits=e.ws("b_logits", (N, vpad))))
-            import ctypes
             rows_ptr = (ctypes.c_void_p * len(per))(*[p["logits"].data_ptr() for p in per])
             for t in range(1, T + 1):
-                a_old, a_new = anc[(t - 1) & 1], anc[t & 1]
                 for p in per:
                     e = p["e"]
-                    x, xb = e._decode_step(t, N, bm, tok, a_old, p["sem"], p["ckv"], p["skv"], p["Lk"], "b_", akv=p["akv"])
+                    x, xb = e._decode_step(t, N, bm, v["tok"], v["anc"][(t - 1) & 1], p["sem"], p["ckv"], p["skv"], p["Lk"], "b_",
+                                           akv=p["akv"])
                     e.gemm(xb if xb is not None else x, e.w["vocab"], None, p["logits"][:, : self.V])
                 self.call("care_ensemble_select", rows_ptr, len(per), vpad, self.V, bm, ptr(cval), ptr(cidx), N)
-                self.call("care_beam_advance", ptr(cval), ptr(cidx), ptr(scores), bm, ptr(tok), ptr(a_old), ptr(a_new),
-                     ptr(done), ptr(nfin), cap, ptr(fscore), ptr(flen), ptr(fhyp), t, T, need, EOS, self.V, T + 1, B)
-            return nfin, fscore, flen, fhyp
-        sel = self._beam_select_ws("b_", N)
-        ckv = self.cross_src(mem, N)
-        akv = self.attr_kv(sem_embs) if self.attr_att else None
-        skv = [self.ws("b_skv%d" % li, (N, T, 2 * d), self.wt) for li in range(self.n_layers)]
-        for t in range(1, T + 1):
-            a_old, a_new = anc[(t - 1) & 1], anc[t & 1]
-            x, xb = self._decode_step(t, N, bm, tok, a_old, sem, ckv, skv, Lk, "b_", akv=akv)
-            self._beam_select("b_", sel, x, xb, N, bm, cval, cidx)
-            self.call("care_beam_advance", ptr(cval), ptr(cidx), ptr(scores), bm, ptr(tok), ptr(a_old), ptr(a_new),
-                 ptr(done), ptr(nfin), cap, ptr(fscore), ptr(flen), ptr(fhyp), t, T, need, EOS, self.V, T + 1, B)
-        return nfin, fscore, flen, fhyp
+                self._beam_advance(v, t, bm, need, cval, cidx)
+        else:
+            v["ckv"] = self.cross_src(mem, N)
+            v["akv"] = self.attr_kv(sem_embs) if self.attr_att else None
+            v["skv"] = [self.ws("b_skv%d" % li, (N, T, 2 * d), self.wt) for li in range(self.n_layers)]
+            self._beam_steps(v, 1, T, bm, need)
+        return v["nfin"], v["fscore"], v["flen"], v["fhyp"]

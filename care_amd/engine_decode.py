@@ -1,7 +1,9 @@
 """HipEngine, the decoder: one decode step (`_decode_step`: DecoderLayer, models/components/Layers.py:157-228), the
-teacher-forced forward and fused scoring (Framework.py:215-237), and the greedy loops - fixed length, early exit with
-compaction, batch lanes (models/Translator.py:35-133 with beam_size 1).  Methods of care_amd.engine.HipEngine."""
+teacher-forced forward and fused scoring (Framework.py:215-237), the greedy loops - fixed length, early exit with
+compaction, batch lanes (models/Translator.py:35-133 with beam_size 1) - and what every segmented pass shares: the segment
+loop (`_segments`) and the mover of per-clip tensors (`_move_clips`).  Methods of care_amd.engine.HipEngine."""
 import ctypes
+import functools
 import os
 from typing import Dict, List, Optional
 
@@ -81,15 +83,16 @@ class DecodeMixin:
         return y, yb
 
     # ------------------------------------------------------------------ teacher-forced decoder
-    def _dense_ln(self, ctx, name, res, out, outb, rows, tag):
+    def _dense_ln(self, ctx, name, res, out, outb, ws, tag, add_tag=None):
         """dense -> (+ residual) -> LayerNorm of an attention block (SubLayers.py:69-79): one fused kernel from
-        ~10 K rows (forms.fuse_ln), the A-stationary GEMM + LayerNorm pair below."""
+        ~10 K rows (forms.fuse_ln, by the pass's INITIAL row count), the A-stationary GEMM + LayerNorm pair below.
+        ws: prefix of the projection's workspace; tag: of the launches (tag_ln, or tag_gemm and add_tag)."""
         w = self.w
         if self.plan.fuse_ln:
             return self.gemm_ln(ctx, w[name + "_o_w"], w[name + "_o_b"], res, w[name + "_g"], w[name + "_be"], out, outb,
                                 tag=tag + "_ln", Wp=w.get(name + "_o_w#packed"))
-        o = self.gemm(ctx, w[name + "_o_w"], w[name + "_o_b"], self.ws("tf_o", (rows, self.d)), tag=tag + "_gemm")
-        return self.add_ln(o, res, w[name + "_g"], w[name + "_be"], out, outb)
+        o = self.gemm(ctx, w[name + "_o_w"], w[name + "_o_b"], self.ws(ws + "o", (ctx.shape[0], self.d)), tag=tag + "_gemm")
+        return self._res_ln(o, res, w[name + "_g"], w[name + "_be"], out, outb, tag=add_tag)
 
     def _decode_full_fast(self, x, xb, ids32, N, t, B, Lk, per_clip, ckv, akv, want_logits, hidden_fp32=True):
         """The teacher-forced decoder (Decoder/Transformer.py:161-268 with Lq = t) on the kernels of the decode path:
@@ -107,7 +110,7 @@ class DecodeMixin:
             self.call("care_attention_seq", ptr(qkv), 3 * d, ptr(qkv[:, d:]), ptr(qkv[:, 2 * d:]), t * 3 * d, 3 * d, 1, t, 1, t,
                  ptr(ids32), t, PAD, None, 0, ptr(ctx), d, N, H, tag="tf_self_attn")
             x1, x1b = self.ws("tf_x1", (rows, d)), self.wsb("tf_x1", (rows, d))
-            self._dense_ln(ctx, nm, x, x1, x1b, rows, "tf_dxd")
+            self._dense_ln(ctx, nm, x, x1, x1b, "tf_", "tf_dxd")
             nm = "d{}_ca".format(li)
             hb = w["d{}_hb".format(li)]
             # (d x d with a 16-bit output: the LDS-tiled kernel, as in the decode step - *measured* 118784 rows 94 -> 84 us)
@@ -119,7 +122,7 @@ class DecodeMixin:
             self.call("care_attention_seq", ptr(q2), d, ptr(kv), ptr(kv[:, d:]), Lk * 2 * d, 2 * d, per_clip, Lk, 0, t,
                  None, 0, PAD, ptr(hb), hb.stride(0) if hb is not None else 0, ptr(ctx), d, N, H, tag="tf_cross_attn")
             x2, x2b = self.ws("tf_x2", (rows, d)), self.wsb("tf_x2", (rows, d))
-            self._dense_ln(ctx, nm, x1, x2, x2b, rows, "tf_dxd")
+            self._dense_ln(ctx, nm, x1, x2, x2b, "tf_", "tf_dxd")
             if self.attr_att:
                 nm = "d{}_aa".format(li)
                 q3 = self.gemm(x2b, w[nm + "_q_w"], w[nm + "_q_b"], bfw("tf_q2b", (rows, d)), tag="tf_dxd_gemm")
@@ -127,7 +130,7 @@ class DecodeMixin:
                 self.call("care_attention_seq", ptr(q3), d, ptr(kv), ptr(kv[:, d:]), self.topk * 2 * d, 2 * d, per_clip,
                      self.topk, 0, t, None, 0, PAD, None, 0, ptr(ctx), d, N, H, tag="tf_attr_attn")
                 y, yb = self.ws("tf_x2a", (rows, d)), self.wsb("tf_x2a", (rows, d))
-                self._dense_ln(ctx, nm, x2, y, yb, rows, "tf_dxd")
+                self._dense_ln(ctx, nm, x2, y, yb, "tf_", "tf_dxd")
                 x2, x2b = y, yb
             last = li == self.n_layers - 1
             xb = self.wsb("tf_x3", (rows, d))
@@ -340,12 +343,7 @@ class DecodeMixin:
             ctx = self.attention(q, flat, flat[:, d:], self._ctx(tag, N), T * 2 * d, 2 * d, 1, t, anc=anc,
                                  pad_tok=tok, tag="step_self_attn")
             x1, x1b = self.ws(tag + "x1", (N, d)), self.wsb(tag + "x1", (N, d))
-            if fuse_ln:
-                self.gemm_ln(ctx, w[nm + "_o_w"], w[nm + "_o_b"], x, w[nm + "_g"], w[nm + "_be"], x1, x1b,
-                             tag="step_dxd_ln", Wp=w.get(nm + "_o_w#packed"))
-            else:
-                o = self.gemm(ctx, w[nm + "_o_w"], w[nm + "_o_b"], self.ws(tag + "o", (N, d)), tag="step_dxd_gemm")
-                self._res_ln(o, x, w[nm + "_g"], w[nm + "_be"], x1, x1b, tag="step_add_ln")
+            self._dense_ln(ctx, nm, x, x1, x1b, tag, "step_dxd", "step_add_ln")
             nm = "d{}_ca".format(li)
             hb = w["d{}_hb".format(li)]
             x1in, x1inb = self._ln_in(x1, x1b, w[nm + "_g"], w[nm + "_be"], tag + "ca")
@@ -379,12 +377,7 @@ class DecodeMixin:
                 ctx = self.attention(q2, kv, kv[:, d:], self._ctx(tag, N), Lk * 2 * d, 2 * d, rows_per_clip, Lk,
                                      bias=hb, tag="step_cross_attn")
             x2, x2b = self.ws(tag + "x2", (N, d)), self.wsb(tag + "x2", (N, d))
-            if fuse_ln:
-                self.gemm_ln(ctx, w[nm + "_o_w"], w[nm + "_o_b"], x1, w[nm + "_g"], w[nm + "_be"], x2, x2b,
-                             tag="step_dxd_ln", Wp=w.get(nm + "_o_w#packed"))
-            else:
-                o = self.gemm(ctx, w[nm + "_o_w"], w[nm + "_o_b"], self.ws(tag + "o", (N, d)), tag="step_dxd_gemm")
-                self._res_ln(o, x1, w[nm + "_g"], w[nm + "_be"], x2, x2b, tag="step_add_ln")
+            self._dense_ln(ctx, nm, x1, x2, x2b, tag, "step_dxd", "step_add_ln")
             if self.attr_att:
                 x2, x2b = self._attr_block(li, x2, x2b, akv, rows_per_clip, tag)
             x, xb = self.ws(tag + "x3_%d" % (li & 1), (N, d)), self.wsb(tag + "x3_%d" % (li & 1), (N, d))
@@ -402,6 +395,29 @@ class DecodeMixin:
             x, xb = xf, xfb
         return x, xb
 
+    def _greedy_steps(self, v, t0, t1, last):
+        """Steps t0 .. t1 of the greedy decode on the n rows of state `v` (fed, score, length, fin, x0, x0b, sem, ckv, akv,
+        skv, Lk, tag, n); up to step `last` - 1 the token choice also embeds the next step's input."""
+        n, T, d, w = v["n"], self.T, self.d, self.w
+        parts = self.vocab_parts(n)
+        pmax, psum = self.ws(v["tag"] + "pmax", (n, parts)), self.ws(v["tag"] + "psum", (n, parts))
+        pidx = self.ws(v["tag"] + "pidx", (n, parts), torch.int32)
+        for t in range(t0, t1 + 1):
+            x, xb = self._decode_step(t, n, 1, v["fed"], None, v["sem"], v["ckv"], v["skv"], v["Lk"], v["tag"], akv=v["akv"],
+                                      embedded=t > 1)
+            self.vocab_argmax(x, xb, n, pmax, pidx, psum)
+            update = (ptr(pmax), ptr(pidx), ptr(psum), parts, ptr(v["fed"]), T + 1, ptr(v["score"]), ptr(v["length"]),
+                      ptr(v["fin"]), t, T, EOS, n)
+            if t < last:  # the token choice and, in the same launch, its embedding = the input of step t + 1
+                self.call("care_greedy_update_embed", *update, ptr(w["word"]), ptr(w["pos"]), ptr(v["sem"]), 1, ptr(w["emb_g"]),
+                          ptr(w["emb_be"]), self.eps, ptr(v["x0"]), ptr(v["x0b"]), d, d, tag="step_update_embed")
+            else:
+                self.call("care_greedy_update", *update)
+
+    def _greedy_init(self, v):
+        v["fed"].zero_(); v["fed"][:, 0] = BOS
+        v["score"].zero_(); v["length"].zero_(); v["fin"].zero_()
+
     def greedy(self, mem: torch.Tensor, sem: Optional[torch.Tensor], steps: Optional[int] = None,
                sem_embs: Optional[torch.Tensor] = None):
         """Greedy decoding (= beam search with beam_size 1, models/Wrapper.py:34-35) of B clips.
@@ -413,32 +429,18 @@ class DecodeMixin:
         T = self.T
         steps = T if steps is None else steps
         mem = mem.to(self.device, mem.dtype if mem.dtype == self.h16 else torch.float32)  # bf16: lean encode
-        sem = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
         length, score, fed = self.ws_block("g_out", [((B,), torch.int32), ((B,), torch.float32), ((B, T + 1), torch.int32)])
-        fin = self.ws("g_fin", (B,), torch.int32)
-        fed.zero_(); fed[:, 0] = BOS
-        score.zero_(); length.zero_(); fin.zero_()
-        ckv = self.cross_src(mem, B)
-        akv = self.attr_kv(sem_embs) if self.attr_att else None
-        skv = [self.ws("g_skv%d" % li, (B, T, 2 * d), self.wt) for li in range(self.n_layers)]
-        parts = self.vocab_parts(B)
-        pmax = self.ws("g_pmax", (B, parts))
-        pidx = self.ws("g_pidx", (B, parts), torch.int32)
-        psum = self.ws("g_psum", (B, parts))
-        x0, x0b = self.ws("g_x0", (B, d)), self.wsb("g_x0", (B, d))  # the workspaces _decode_step embeds into
-        for t in range(1, steps + 1):
-            x, xb = self._decode_step(t, B, 1, fed, None, sem, ckv, skv, Lk, "g_", akv=akv, embedded=t > 1)
-            self.vocab_argmax(x, xb, B, pmax, pidx, psum)
-            if t < steps:  # the token choice and, in the same launch, its embedding = the input of step t + 1
-                self.call("care_greedy_update_embed", ptr(pmax), ptr(pidx), ptr(psum), parts, ptr(fed), T + 1, ptr(score),
-                     ptr(length), ptr(fin), t, T, EOS, B, ptr(self.w["word"]), ptr(self.w["pos"]), ptr(sem), 1,
-                     ptr(self.w["emb_g"]), ptr(self.w["emb_be"]), self.eps, ptr(x0), ptr(x0b), d, d, tag="step_update_embed")
-            else:
-                self.call("care_greedy_update", ptr(pmax), ptr(pidx), ptr(psum), parts, ptr(fed), T + 1, ptr(score),
-                     ptr(length), ptr(fin), t, T, EOS, B)
+        v = dict(tag="g_", n=B, Lk=Lk, fed=fed, score=score, length=length, fin=self.ws("g_fin", (B,), torch.int32),
+                 sem=sem.to(self.device, torch.float32).contiguous() if sem is not None else None,
+                 x0=self.ws("g_x0", (B, d)), x0b=self.wsb("g_x0", (B, d)))  # (x0: the workspaces _decode_step embeds into)
+        self._greedy_init(v)
+        v["ckv"] = self.cross_src(mem, B)
+        v["akv"] = self.attr_kv(sem_embs) if self.attr_att else None
+        v["skv"] = [self.ws("g_skv%d" % li, (B, T, 2 * d), self.wt) for li in range(self.n_layers)]
+        self._greedy_steps(v, 1, steps, steps)
         return fed, length, score
 
-    # ------------------------------------------------------------------ greedy with early exit + compaction
+    # ------------------------------------------------------------------ segments with early exit + compaction
     def _call_rows(self, fn, src, dst, idx, n):
         """care_gather_rows / care_scatter_rows on tensors whose first dim is the row."""
         rb = src[0].numel() * src.element_size()
@@ -449,6 +451,40 @@ class DecodeMixin:
         that the captured segments of different batches meet the same few shapes."""
         g = max(64, cap // 32)
         return min(cap, (active + g - 1) // g * g)
+
+    def _segments(self, B, per, S, key, run, later_key, later, use_graph, cnt=None, count_last=False, compact=None, **extra):
+        """The segment loop of the segmented passes (greedy_early_exit, beam_early_exit, translate_beam_chain): steps 1 .. S
+        through `run()` -> (enc, state) under `key`, then S steps at a time through `later(state, t, t1)` under
+        `later_key(t, t1, clips, parity)`, each segment replayed from a hipGraph of its own (_replay).  Between two segments
+        ONE counter comes back to the host (`cnt`: the clips still live; None: no early exit, nothing is read; count_last:
+        also after step T): none live ends the pass; at most 3/4 of the slots in use, on 2048 rows or more (`per` rows per
+        clip), has `compact(state, parity, clips, active)` move the survivors to the other buffer set (None: never).
+        `last_decode` is published after the first segment and updated as the pass goes (tests, bench, the idle hook).
+        Returns (enc, the last state)."""
+        T = self.T
+        try:
+            enc, v = self._replay(key, run, use_graph)
+            n, par, t = B, 0, min(S, T) + 1
+            stats = self.last_decode = dict(clips=B, steps=t - 1, row_steps=B * per * (t - 1), compactions=0, **extra)
+            while t <= T or (count_last and cnt is not None):
+                if cnt is not None:
+                    active = self._host_count(cnt)  # the one host round trip per segment
+                    if active == 0 or t > T:
+                        break
+                    m = self._slot_bucket(active, B) if compact is not None and n * per >= 2048 else n
+                    if m * 4 <= n * 3:
+                        v, n, par = compact(v, par ^ 1, m, active), m, par ^ 1
+                        stats["compactions"] += 1
+                t1 = min(t + S - 1, T)
+                # (a closure handed to _replay runs again at capture time: it holds THIS segment's state and bounds)
+                key, run = later_key(t, t1, n, par), functools.partial(later, v, t, t1)
+                self._replay(key, run, use_graph)
+                stats["steps"] = t1
+                stats["row_steps"] += n * per * (t1 - t + 1)
+                t = t1 + 1
+        finally:
+            self._ws_cap = None
+        return enc, v
 
     def greedy_early_exit(self, feats: List[torch.Tensor], lean: bool = False, use_graph: bool = True,
                           plan: Optional[forms.PassPlan] = None):
@@ -478,39 +514,22 @@ class DecodeMixin:
         out_len, out_score, out_fed = self.ws_block("ge_out", [((B,), torch.int32), ((B,), torch.float32), ((B, T + 1), torch.int32)])
         idx = self.ws("ge_idx", (B,), torch.int32)
         cnt = self.ws("ge_cnt", (1,), torch.int32)
-        st = {}
 
         def state(par, n):
             """Views of buffer set `par` for n slots (allocated at full size once)."""
             self._ws_cap = (n, B)
             tag = "g%d_" % par
-            v = dict(tag=tag, n=n,
-                     fed=self.ws(tag + "fed", (n, T + 1), torch.int32), score=self.ws(tag + "score", (n,)),
-                     length=self.ws(tag + "len", (n,), torch.int32), fin=self.ws(tag + "fin", (n,), torch.int32),
-                     clip=self.ws(tag + "clip", (n,), torch.int32),
-                     x0=self.ws(tag + "x0", (n, d)), x0b=self.wsb(tag + "x0", (n, d)),
-                     skv=[self.ws(tag + "skv%d" % li, (n, T, 2 * d), self.wt) for li in range(self.n_layers)])
-            return v
+            return dict(tag=tag, n=n, B=B, Lk=self.Lk,
+                        fed=self.ws(tag + "fed", (n, T + 1), torch.int32), score=self.ws(tag + "score", (n,)),
+                        length=self.ws(tag + "len", (n,), torch.int32), fin=self.ws(tag + "fin", (n,), torch.int32),
+                        clip=self.ws(tag + "clip", (n,), torch.int32),
+                        x0=self.ws(tag + "x0", (n, d)), x0b=self.wsb(tag + "x0", (n, d)),
+                        skv=[self.ws(tag + "skv%d" % li, (n, T, 2 * d), self.wt) for li in range(self.n_layers)])
 
-        def run_steps(v, t0, t1, enc=None):
-            n = v["n"]
-            self._ws_cap = (n, B)
-            parts = self.vocab_parts(n)
-            pmax, psum = self.ws(v["tag"] + "pmax", (n, parts)), self.ws(v["tag"] + "psum", (n, parts))
-            pidx = self.ws(v["tag"] + "pidx", (n, parts), torch.int32)
-            for t in range(t0, t1 + 1):
-                x, xb = self._decode_step(t, n, 1, v["fed"], None, v["sem"], v["ckv"], v["skv"], self.Lk, v["tag"],
-                                          akv=v["akv"], embedded=t > 1)
-                self.vocab_argmax(x, xb, n, pmax, pidx, psum)
-                if t < T:
-                    self.call("care_greedy_update_embed", ptr(pmax), ptr(pidx), ptr(psum), parts, ptr(v["fed"]), T + 1,
-                         ptr(v["score"]), ptr(v["length"]), ptr(v["fin"]), t, T, EOS, n, ptr(self.w["word"]),
-                         ptr(self.w["pos"]), ptr(v["sem"]), 1, ptr(self.w["emb_g"]), ptr(self.w["emb_be"]), self.eps,
-                         ptr(v["x0"]), ptr(v["x0b"]), d, d, tag="step_update_embed")
-                else:
-                    self.call("care_greedy_update", ptr(pmax), ptr(pidx), ptr(psum), parts, ptr(v["fed"]), T + 1,
-                         ptr(v["score"]), ptr(v["length"]), ptr(v["fin"]), t, T, EOS, n)
-            self.call("care_active_slots", ptr(v["fin"]), n, ptr(idx), ptr(cnt))
+        def run_steps(v, t0, t1):
+            self._ws_cap = (v["n"], B)
+            self._greedy_steps(v, t0, t1, T)
+            self.call("care_active_slots", ptr(v["fin"]), v["n"], ptr(idx), ptr(cnt))
 
         def first_segment():
             """encode, state initialisation and steps 1 .. S on all B slots of buffer set 0."""
@@ -519,8 +538,7 @@ class DecodeMixin:
             mem = enc["encoder_hidden_states"]
             sem = enc.get("semantic_hidden_states")
             v = state(0, B)
-            v["fed"].zero_(); v["fed"][:, 0] = BOS
-            v["score"].zero_(); v["length"].zero_(); v["fin"].zero_()
+            self._greedy_init(v)
             torch.add(self._arange(B), 0, out=v["clip"])   # (an elementwise kernel, not a memcpy node in the captured graph: see csrc/decode_resident.h, res_zero_kernel)
             v["sem"] = sem.to(self.device, torch.float32).contiguous() if sem is not None else None
             self._ws_cap = None  # cross_src / attr_kv work on all B clips
@@ -529,34 +547,22 @@ class DecodeMixin:
             run_steps(v, 1, min(S, T))
             return enc, v
 
-        replayable = lambda key, fn: self._replay(key, fn, use_graph)
-
-        try:
-            enc, v = replayable(forms.graph_key("gseg0", plan, feats, S), first_segment)
-            par, t = 0, min(S, T) + 1
-            stats = dict(clips=B, steps=t - 1, row_steps=B * (t - 1), compactions=0)
-            self.last_decode = stats  # what the last pass actually ran (tests, bench)
-            while True:
-                active = self._host_count(cnt)  # the one host round trip per segment
-                if active == 0 or t > T:
-                    break
-                n_new = self._slot_bucket(active, B)
-                if n_new * 4 <= v["n"] * 3 and v["n"] >= 2048:
-                    v = self._compact(v, state(par ^ 1, n_new), idx, active, out_fed, out_len, out_score)
-                    par ^= 1
-                    stats["compactions"] += 1
-                t1 = min(t + S - 1, T)
-                vv = v
-                replayable(("gseg", plan, t, t1, v["n"], par), lambda: run_steps(vv, t, t1))
-                stats["steps"] = t1
-                stats["row_steps"] += v["n"] * (t1 - t + 1)
-                t = t1 + 1
+        def flush(v):
+            """results of every slot of v -> the per-clip outputs"""
             n = v["n"]
             self._call_rows("care_scatter_rows", v["fed"], out_fed, v["clip"], n)
             self._call_rows("care_scatter_rows", v["length"].view(n, 1), out_len.view(B, 1), v["clip"], n)
             self._call_rows("care_scatter_rows", v["score"].view(n, 1), out_score.view(B, 1), v["clip"], n)
-        finally:
-            self._ws_cap = None
+
+        def compact(v, par, m, active):
+            w = state(par, m)
+            flush(v)
+            return self._compact(v, w, idx, active)
+
+        enc, v = self._segments(B, 1, S, forms.graph_key("gseg0", plan, feats, S), first_segment,
+                                lambda t, t1, n, par: ("gseg", plan, t, t1, n, par), run_steps, use_graph, cnt=cnt,
+                                count_last=True, compact=compact)
+        flush(v)
         return enc, out_fed, out_len, out_score
 
     def _arange(self, n):
@@ -564,23 +570,11 @@ class DecodeMixin:
         torch.arange(n, device=self.device, dtype=torch.int32, out=t)  # refilled: an evicted buffer comes back empty
         return t
 
-    def _compact(self, v, w, idx, active, out_fed, out_len, out_score):
-        """Results of every slot of `v` -> the per-clip outputs; then the first w['n'] slots of the
-        partition `idx` (active ones first, ended ones as padding) -> buffer set `w`."""
-        n, m = v["n"], w["n"]
-        B = out_fed.shape[0]
-        self._call_rows("care_scatter_rows", v["fed"], out_fed, v["clip"], n)
-        self._call_rows("care_scatter_rows", v["length"].view(n, 1), out_len.view(B, 1), v["clip"], n)
-        self._call_rows("care_scatter_rows", v["score"].view(n, 1), out_score.view(B, 1), v["clip"], n)
-        for k in ("fed", "x0", "x0b"):
-            if v[k] is not None:
-                self._call_rows("care_gather_rows", v[k], w[k], idx, m)
-        for k in ("score", "length", "fin", "clip"):
-            self._call_rows("care_gather_rows", v[k].view(n, 1), w[k].view(m, 1), idx, m)
-        for a, b in zip(v["skv"], w["skv"]):
-            self._call_rows("care_gather_rows", a, b, idx, m)
-        tag = w["tag"]
-        self._ws_cap = (m, B)
+    def _move_clips(self, v, w, idx, active):
+        """The per-clip tensors of state `v` (guidance vector, cross-attention source, concept K/V) -> the first w['n'] clips
+        of buffer set `w` in the order of the partition `idx`; slots from `active` on are padding: ended clips whose results
+        are already out.  The caller has gathered the state of its own and set `_ws_cap`."""
+        n, m, tag = v["n"], w["n"], w["tag"]
 
         def moved(name, src, per=1):
             """Per-clip tensor with `per` rows per clip ([n * per, ...] or, per = 1, [n, ...]) -> m clips."""
@@ -597,8 +591,21 @@ class DecodeMixin:
         else:                            # projected K/V: [n * Lk, 2d] per layer
             w["ckv"] = [moved("ckv%d" % i, kv, self.Lk) for i, kv in enumerate(v["ckv"])]
         w["akv"] = [moved("akv%d" % i, kv, self.topk) for i, kv in enumerate(v["akv"])] if v["akv"] is not None else None
-        w["clip"][active:].fill_(-1)     # padding slots: ended clips whose results are already out
+        w["clip"][active:].fill_(-1)
         return w
+
+    def _compact(self, v, w, idx, active):
+        """The first w['n'] slots of the partition `idx` (active ones first, ended ones as padding) -> buffer set `w`."""
+        n, m = v["n"], w["n"]
+        for k in ("fed", "x0", "x0b"):
+            if v[k] is not None:
+                self._call_rows("care_gather_rows", v[k], w[k], idx, m)
+        for k in ("score", "length", "fin", "clip"):
+            self._call_rows("care_gather_rows", v[k].view(n, 1), w[k].view(m, 1), idx, m)
+        for a, b in zip(v["skv"], w["skv"]):
+            self._call_rows("care_gather_rows", a, b, idx, m)
+        self._ws_cap = (m, v["B"])
+        return self._move_clips(v, w, idx, active)
 
     def translate_greedy(self, feats: List[torch.Tensor], use_graph: bool = True, lean: bool = False,
                          early_exit: Optional[bool] = None):

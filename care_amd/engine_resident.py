@@ -135,27 +135,18 @@ class ResidentMixin:
             plan = self._begin_pass(self.plan_for(B, bm, need, lean=lean, early_exit=early_exit))
         S = max(1, self.chain_segment_steps) if early_exit else T
 
+        def steps(enc, t0, t1, count_live=True):
+            return self.beam_chain_steps(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"), bm, need, t0, t1,
+                                         sem_embs=enc.get("semantic_embs"), count_live=count_live)
+
         def first():
             enc = self.encode(feats, plan.lean, static=True, small=plan.small)
-            v = self.beam_chain_steps(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"), bm, need, 1, min(S, T),
-                                      sem_embs=enc.get("semantic_embs"), count_live=early_exit)
-            return enc, v
+            return enc, dict(steps(enc, 1, min(S, T), early_exit), enc=enc)
 
-        enc, v = self._replay(forms.graph_key("bchain", plan, feats, 0, S), first, use_graph)
-        t = min(S, T) + 1
-        stats = dict(clips=B, steps=t - 1, row_steps=B * bm * (t - 1), compactions=0, chain=True)
-        self.last_decode = stats
-        while t <= T:
-            if early_exit and self._host_count(v["cnt"]) == 0:
-                break
-            t1 = min(t + S - 1, T)
-            tt = t
-            self._replay(forms.graph_key("bchain", plan, feats, tt, t1),
-                         lambda: self.beam_chain_steps(enc["encoder_hidden_states"], enc.get("semantic_hidden_states"), bm, need,
-                                                       tt, t1, sem_embs=enc.get("semantic_embs")), use_graph)
-            stats["steps"] = t1
-            stats["row_steps"] += B * bm * (t1 - tt + 1)
-            t = t1 + 1
+        enc, v = self._segments(B, bm, S, forms.graph_key("bchain", plan, feats, 0, S), first,
+                                lambda t, t1, n, par: forms.graph_key("bchain", plan, feats, t, t1),
+                                lambda v, t, t1: steps(v["enc"], t, t1), use_graph,
+                                cnt=self.ws("cb_cnt", (1,), torch.int32) if early_exit else None, chain=True)
         return enc, v["nfin"], v["fscore"], v["flen"], v["fhyp"]
 
     def greedy_resident(self, mem: torch.Tensor, sem: Optional[torch.Tensor], sem_embs: Optional[torch.Tensor] = None,
