@@ -2,8 +2,11 @@
 
 Public seam (mirrors the reference's two factories):
     from care_amd import get_framework, get_translator
+and, for training, the reference's criteria behind `misc.Crit`'s interface (care_amd/criterion.py):
+    from care_amd import get_criterion
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
+from .criterion import Criterion, LanguageGeneration, NoisyOrMIL, get_criterion  # noqa: F401
 
-__all__ = ["get_framework", "get_translator"]
+__all__ = ["get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL"]

@@ -12,7 +12,7 @@ import torch
 CARE_F32, CARE_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 ACT_CODES = {"linear": ACT_NONE, "relu": ACT_RELU, "gelu": ACT_GELU}
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _ERRORS = {-1: "CARE_EINVAL (null pointer / bad size)", -2: "CARE_EALIGN (alignment)",
            -3: "CARE_ESHAPE (unsupported shape)", -4: "CARE_EDTYPE (unknown dtype/activation)"}
@@ -93,6 +93,10 @@ SIGNATURES = {
     "care_concept_bwd": [_P, _L, _P, _L, _P, _P, _L, _I, _I, _P],
     "care_attn_pv": [_P, _P, _L, _L, _P, _L, _I, _I, _I, _I, _F, _U, _P],
     "care_attn_bwd": [_P, _L, _P, _P, _L, _L, _P, _P, _L, _P, _L, _P, _P, _L, _L, _P, _I, _I, _I, _I, _I, _F, _U, _P],
+    "care_lang_loss_fwd": [_P, _L, _L, _I, _I, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "care_lang_loss_bwd": [_P, _L, _L, _I, _I, _P, _P, _P, _F, _P, _P, _L, _L, _I, _I, _P],
+    "care_noisy_or_bce_fwd": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _I, _P],
+    "care_noisy_or_bce_bwd": [_P, _L, _P, _L, _P, _P, _P, _L, _I, _I, _P],
     "care_active_slots": [_P, _I, _P, _P, _P],
     "care_gather_rows": [_P, _L, _P, _L, _P, _I, _L, _P],
     "care_scatter_rows": [_P, _L, _P, _L, _P, _I, _L, _P],

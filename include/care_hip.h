@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CARE_ABI_VERSION 22
+#define CARE_ABI_VERSION 23
 
 enum { CARE_F32 = 0, CARE_BF16 = 1 };
 enum { CARE_ACT_NONE = 0, CARE_ACT_RELU = 1, CARE_ACT_GELU = 2 };
@@ -627,6 +627,49 @@ int care_gemm_kn(const float* A, int64_t lda, int a_is_km, const float* B, int64
 int care_gemm_kn_splitk(const float* A, int64_t lda, int a_is_km, const float* B, int64_t ldb, float* C, int64_t ldc,
                         int64_t c_slab, int M, int N, int K, int ksplit, void* stream);
 int care_gemm_kn_splits(int M, int N, int K);
+
+/*
+ * Training criteria (misc/Crit/base.py:20-47 CritBase.__call__ around the two `_step`s below; driven by Criterion.get_loss
+ * from models/Wrapper.py:423-435; care_amd/criterion.py).  fp32 arithmetic in both libraries; no floating-point atomics:
+ * row results go to per-row arrays and the sums over rows are added in a fixed order by a one-workgroup reduce that the
+ * forward entry points enqueue behind the row kernel - two calls give identical bits.
+ *
+ * care_lang_loss_fwd: LanguageGeneration._step (misc/Crit/crit_lang.py:27-73: log_softmax, NLLLoss, the label-smoothing
+ *   mean, the PAD mask) with calculate_word_acc / calculate_perplexity (:75-103) for `rows` label positions.  Row r reads the
+ *   V fp32 logits at logits + (r / rows_per_seq) * seq_stride + (r % rows_per_seq) * ld - with seq_stride = (rows_per_seq + 1) * ld
+ *   the `logits[:, :-1, :]` case of crit_lang.py:49-50 runs without a copy - and writes
+ *     rmax[r] = max x, lsum[r] = log sum exp(x - max), lse[r] = rmax + lsum, logp[r] = x[y] - lse,
+ *     pred[r] = arg-max column (lowest index on ties, as care_score_logits),
+ *     row_loss[r] = (1 - eps) (lse - x[y]) + eps (lse - mean(x)).
+ *   One workgroup per row; the row is read ONCE while V <= 16384 (kept in registers: 16 float4 per lane of 256; 16-byte loads
+ *   after peeling to alignment, any ld and any 4-byte-aligned base) and twice beyond (the re-reading form).  Rows whose label
+ *   is PAD (0) are not read: lse = rmax = lsum = logp = row_loss = 0, pred = 0.  A label outside [0, V) is never dereferenced: the row is
+ *   treated like a PAD row and counted.  Behind the row kernel:
+ *     sums[0] = sum row_loss, sums[1] = sum -logp (fp32, fixed order);
+ *     counts[0] = rows with pred == label, counts[1] = non-PAD rows, counts[2] = rows with a label outside [0, V) (n_bad);
+ *     acc (optional, 5 doubles): acc[0..1] += sums, acc[2..4] += counts - the recorders of Criterion.get_loss
+ *     (base.py:95) and crit_lang.py:83-103 without a host synchronisation; one thread adds, in stream order.
+ * care_lang_loss_bwd: the autograd backward of the above to the logits: for live rows
+ *     dlogits[r, c] = g (exp(x[c] - lse[r]) - (1 - eps) [c == y] - eps / V),   g = *g (a DEVICE scalar: the upstream
+ *   gradient is not known to the host), one read and one write per live row; the exponent is taken as (x - rmax) - lsum, the
+ *   forward's two parts of lse (exact where the probability is; x - lse rounds at an ulp of |lse|); PAD rows, rows with a bad label and the positions
+ *   rows_per_seq .. seq_rows - 1 of every sequence (the dropped last position) are zero-filled - dlogits arrives uninitialised.
+ *   dlogits row (s, p), p < seq_rows, lies at dlogits + s * dseq_stride + p * ldd; rows must be a multiple of rows_per_seq.
+ * care_noisy_or_bce_fwd / _bwd: NoisyOrMIL._step (misc/Crit/crit_attribute.py:38-48) and its backward: p = clamp(preds, 0.01,
+ *   0.99), row_loss[b] = -sum_{c < K} (y log p + (1 - y) log(1 - p)) / denom[b], denom[b] = max(1, sum_{c < K} y); labels fp32
+ *   [B, ldl >= K], the first K columns used.  dpreds[b, c] = -g (y / p - (1 - y) / (1 - p)) / denom[b] where 0.01 <= preds <= 0.99
+ *   and 0 elsewhere (torch.clamp's rule).  One wave per clip.  sums[0] = sum row_loss (fixed order), acc (optional, 1 double) +=.
+ */
+int care_lang_loss_fwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V, const int32_t* labels,
+                       float eps, float* lse, float* rmax, float* lsum, float* logp, int32_t* pred, float* row_loss, float* sums,
+                       int32_t* counts, double* acc, int rows, void* stream);
+int care_lang_loss_bwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V, const int32_t* labels,
+                       const float* rmax, const float* lsum, float eps, const float* g, float* dlogits, int64_t ldd,
+                       int64_t dseq_stride, int seq_rows, int rows, void* stream);
+int care_noisy_or_bce_fwd(const float* preds, int64_t ldp, const float* labels, int64_t ldl, float* row_loss, float* denom,
+                          float* sums, double* acc, int B, int K, void* stream);
+int care_noisy_or_bce_bwd(const float* preds, int64_t ldp, const float* labels, int64_t ldl, const float* denom, const float* g,
+                          float* dpreds, int64_t ldd, int B, int K, void* stream);
 
 /*
  * care_decode_resident: the whole greedy decode of a SMALL batch (1 .. a few hundred caption rows) as ONE launch.
