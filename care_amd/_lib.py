@@ -12,7 +12,7 @@ import torch
 CARE_F32, CARE_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 ACT_CODES = {"linear": ACT_NONE, "relu": ACT_RELU, "gelu": ACT_GELU}
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _ERRORS = {-1: "CARE_EINVAL (null pointer / bad size)", -2: "CARE_EALIGN (alignment)",
            -3: "CARE_ESHAPE (unsupported shape)", -4: "CARE_EDTYPE (unknown dtype/activation)"}
@@ -97,6 +97,13 @@ SIGNATURES = {
     "care_lang_loss_bwd": [_P, _L, _L, _I, _I, _P, _P, _P, _F, _P, _P, _L, _L, _I, _I, _P],
     "care_noisy_or_bce_fwd": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _I, _P],
     "care_noisy_or_bce_bwd": [_P, _L, _P, _L, _P, _P, _P, _L, _I, _I, _P],
+    "care_head_live_rows": [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "care_gemm_tile_split3_head_stats": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "care_head_loss_finish": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "care_lang_loss_reduce": [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P],
+    "care_head_grad_scale": [_P, _P, _P],
+    "care_gemm_tile_split3_head_grad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P],
+    "care_pieces_transpose": [_P, _I, _I, _I, _I, _I, _P, _P],
     "care_active_slots": [_P, _I, _P, _P, _P],
     "care_gather_rows": [_P, _L, _P, _L, _P, _I, _L, _P],
     "care_scatter_rows": [_P, _L, _P, _L, _P, _I, _L, _P],

@@ -10,6 +10,13 @@
 * `LanguageGeneration` (crit_lang.py): label-smoothed NLL of the teacher-forced logits with the PAD mask, word accuracy and
   perplexity - care_lang_loss_fwd / care_lang_loss_bwd (csrc/loss.hip): the [N, t, V] logits are read once forward, once
   backward, PAD rows not at all; nothing of the size of the logits is allocated except their gradient.
+  With `model.set_fused_head(True)` (default off) the model hands over a `DeferredLogits` - the decoder's hidden states and
+  the head's weight - instead of logits, and `_HeadLoss` runs the vocabulary projection (Head.py:26-32), the same loss, its
+  metrics and its backward over the LIVE label positions only (about a quarter of a batch of captions): no [rows, V] fp32
+  tensor exists at any point.  The head's products are then ALWAYS split products of pre-scaled fp16 hi / lo pieces (the
+  `fp16x3` form of training.py), whatever TRAIN_GEMM says for the other layers.  Labels on the host (a loader's batch) are
+  counted before their copy, so `get_loss` stays free of host synchronisation; for labels already on the device the count
+  of live rows - 4 bytes - is read back: the one exception.
 * `NoisyOrMIL` (crit_attribute.py): BCE of the clamped concept probabilities over the number of positives, F1@k, mAP -
   care_noisy_or_bce_fwd / _bwd; F1@k / mAP with care_amd/metrics.py's formulas.
 * `Criterion` (base.py:50-113): scales, sums and records them.
@@ -35,11 +42,11 @@ from ._lib import call, ptr
 from .constants import PAD
 from .metrics import TOPK_LIST
 
-__all__ = ["get_criterion", "Criterion", "CritBase", "LanguageGeneration", "NoisyOrMIL"]
+__all__ = ["get_criterion", "Criterion", "CritBase", "LanguageGeneration", "NoisyOrMIL", "DeferredLogits", "head_chunks"]
 
 
 def _need_device(t: torch.Tensor, what: str) -> None:
-    if not isinstance(t, torch.Tensor):
+    if not isinstance(t, (torch.Tensor, DeferredLogits)):
         raise TypeError("`{}` must be a tensor, got {}".format(what, type(t).__name__))
     if t.device.type != "cuda":
         raise RuntimeError("`{}` is on `{}`: the criteria run on the MI355X (there is no CPU fallback)".format(what, t.device))
@@ -84,6 +91,179 @@ class _LangLoss(torch.autograd.Function):
         call("care_lang_loss_bwd", ptr(logits), logits.stride(1), logits.stride(0), t, V, ptr(labels32), ptr(stats[1]), ptr(stats[2]), ctx.eps,
              ptr(g), ptr(d), V, tl * V, tl, N * t)
         return d, None, None, None
+
+
+class DeferredLogits(object):
+    """The logits a training forward with `set_fused_head(True)` did NOT compute: the decoder's hidden states [N, t, d] (an
+    autograd tensor, after the final dropout) and `cls_head.tgt_word_prj.weight` [V, d].  LanguageGeneration runs head and loss
+    fused on it (_HeadLoss); any other consumer calls `.materialize()` for the ordinary logits."""
+
+    def __init__(self, hidden: torch.Tensor, weight: torch.Tensor):
+        if hidden.dim() != 3 or weight.dim() != 2 or hidden.shape[2] != weight.shape[1]:
+            raise ValueError("hidden [N, t, d] and weight [V, d] expected, got {} and {}".format(tuple(hidden.shape), tuple(weight.shape)))
+        self.hidden, self.weight = hidden, weight
+
+    @property
+    def shape(self) -> torch.Size:
+        return torch.Size((self.hidden.shape[0], self.hidden.shape[1], self.weight.shape[0]))
+
+    def size(self, dim: Optional[int] = None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def dim(self) -> int:
+        return 3
+
+    @property
+    def device(self) -> torch.device:
+        return self.hidden.device
+
+    def materialize(self) -> torch.Tensor:
+        """[N, t, V] logits through training.py's `_Linear` (differentiable like the unfused head's)."""
+        from .training import _Linear
+        N, t, d = self.hidden.shape
+        return _Linear.apply(self.hidden.reshape(N * t, d), self.weight, None).view(N, t, -1)
+
+    def __repr__(self):
+        return "DeferredLogits(shape={}, device={})".format(tuple(self.shape), self.device)
+
+
+# Live rows per pass of the fused head's backward: the gradient's fp16 pieces (8 bytes per live row and vocabulary column:
+# [R, 2 ks] and its transpose) are allocated per chunk, so they stay bounded at any batch; dW adds up over the chunks in order.
+# *Measured* on one MI355X (tools/loss_bench.py --head --chunk-rows 0,4096,2048; 512 clips = 3931 live rows; head + both criteria,
+# forward + backward, median of 5 windows, min .. max): whole 1.830 ms (1.775 .. 1.991), 4096 1.777 ms (1.764 .. 1.983) - one chunk
+# at this batch, the same launches as whole -, 2048 2.233 ms (2.166 .. 2.378): a second pass splits W's pieces again and leaves
+# each product half the tiles.  4096: a batch of 512 clips in one pass, 8 x 4096 x 10560 = 346 MB of pieces at most beyond it.
+HEAD_CHUNK_ROWS = 4096
+
+
+def head_chunks(live_rows: int, chunk: Optional[int] = None) -> List[Tuple[int, int]]:
+    """[(first, end), ...] of the live rows in chunks of at most `chunk` (HEAD_CHUNK_ROWS) rows, in order; none for 0 rows."""
+    chunk = HEAD_CHUNK_ROWS if chunk is None else chunk
+    if chunk <= 0:
+        raise ValueError("chunk rows must be positive, got {}".format(chunk))
+    return [(a, min(a + chunk, live_rows)) for a in range(0, max(live_rows, 0), chunk)]
+
+
+def _ceil64(n: int) -> int:
+    return (n + 63) // 64 * 64
+
+
+def _head_forward(hidden2d, W, labels32, eps, acc, live=None):
+    """The forward of _HeadLoss on h [N * tl, d], W [V, d], labels [N, t] (tl >= t: positions past the labels are dead).
+    Returns (sums [2], pred [N * t], counts [3], stats [5, N * t] = lse, max, log sum exp(x - max), logp, row loss per
+    position (zeros at dead ones), saved): every sum in a fixed order, nothing of the size [rows, V]."""
+    from .training import _absmax_slot, _f32c
+    N, t = labels32.shape
+    d, V = hidden2d.shape[1], W.shape[0]
+    tl = hidden2d.shape[0] // N
+    assert hidden2d.shape[0] == N * tl and tl >= t and W.shape[1] == d, (tuple(hidden2d.shape), tuple(W.shape), (N, t))
+    h, Wc = _f32c(hidden2d), _f32c(W)
+    dev, rows = h.device, N * t
+    idx = torch.empty(3, rows, device=dev, dtype=torch.int32)       # live row -> row of h, label position, label
+    cnt = torch.empty(2, device=dev, dtype=torch.int32)
+    call("care_head_live_rows", ptr(labels32), N, t, tl, V, ptr(idx[0]), ptr(idx[1]), ptr(idx[2]), ptr(cnt))
+    R = int(cnt[0].item()) if live is None else int(live)           # device labels: the one 4-byte read-back
+    stats = torch.zeros(5, rows, device=dev, dtype=torch.float32)
+    pred = torch.zeros(rows, device=dev, dtype=torch.int32)
+    sums = torch.empty(2, device=dev, dtype=torch.float32)
+    counts = torch.empty(3, device=dev, dtype=torch.int32)
+    saved = None
+    if R > 0:   # (an all-PAD batch launches nothing with M = 0)
+        h_live = torch.empty(R, d, device=dev, dtype=torch.float32)
+        call("care_gather_rows", ptr(h), h.stride(0) * 4, ptr(h_live), d * 4, ptr(idx[0]), R, d * 4)
+        ksd, parts = _ceil64(d), (V + 63) // 64
+        h_slot, w_slot = _absmax_slot(h_live), _absmax_slot(Wc)
+        a2 = torch.empty(R, 2 * ksd, device=dev, dtype=torch.float16)
+        w3 = torch.empty(V, 3 * ksd, device=dev, dtype=torch.float16)
+        call("care_split_pieces", ptr(h_live), d, R, d, 0, 1, ksd, ptr(a2), 2, h_slot.data_ptr())
+        call("care_split_pieces", ptr(Wc), Wc.stride(0), V, d, 0, 1, ksd, ptr(w3), 3, w_slot.data_ptr())
+        cst = torch.empty(2, R, device=dev, dtype=torch.float32)    # max, log sum exp(x - max) per LIVE row: the backward's
+        for a, b in head_chunks(R):
+            n = b - a
+            pf = torch.empty(4, n, parts, device=dev, dtype=torch.float32)
+            pi = torch.empty(n, parts, device=dev, dtype=torch.int32)
+            call("care_gemm_tile_split3_head_stats", ptr(a2[a:]), ptr(w3), h_slot.data_ptr(), w_slot.data_ptr(), ptr(idx[2][a:]),
+                 ptr(pf[0]), ptr(pi), ptr(pf[1]), ptr(pf[2]), ptr(pf[3]), n, V, ksd)
+            call("care_head_loss_finish", ptr(pf[0]), ptr(pi), ptr(pf[1]), ptr(pf[2]), ptr(pf[3]), parts, ptr(idx[2][a:]),
+                 ptr(idx[1][a:]), V, eps, n, ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(pred), ptr(stats[4]),
+                 ptr(cst[0][a:]), ptr(cst[1][a:]))
+        # W's pieces (6 bytes per weight) are not kept for the backward: split again there from the same |max| - the same bits
+        saved = (h_live, Wc, a2, idx, cst, h_slot, w_slot)
+    call("care_lang_loss_reduce", ptr(stats[4]), ptr(stats[3]), ptr(pred), ptr(labels32), V, rows, ptr(sums), ptr(counts), ptr(acc))
+    return sums, pred, counts, stats, R, saved
+
+
+class _HeadLoss(torch.autograd.Function):
+    """_LangLoss with the vocabulary head inside (Head.py:26-32 + crit_lang.py:49-71): hidden2d [N * tl, d], W [V, d] ->
+    (loss, pred [N, t], counts); backward -> (dhidden [N * tl, d] with dead rows exactly zero, dW [V, d]).  `live`: the number
+    of live label positions when the host knows it (labels counted before their copy); None: read back from the device."""
+
+    @staticmethod
+    def forward(ctx, hidden2d, W, labels32, eps, acc, live=None):
+        N, t = labels32.shape
+        sums, pred, counts, _, R, saved = _head_forward(hidden2d, W, labels32, eps, acc, live)
+        ctx.R, ctx.eps, ctx.h_shape, ctx.w_shape = R, eps, tuple(hidden2d.shape), tuple(W.shape)
+        if saved is not None:
+            ctx.save_for_backward(*saved)
+        pred = pred.view(N, t)
+        ctx.mark_non_differentiable(pred, counts)
+        return sums[0], pred, counts
+
+    @staticmethod
+    def backward(ctx, g, _gp, _gc):
+        from .training import _strided_sum, _x3_slabs
+        (rows_h, d), (V, _) = ctx.h_shape, ctx.w_shape
+        R, eps, dev = ctx.R, ctx.eps, g.device
+        need_dh, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        zeros = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)   # (a fill kernel, not a memset node)
+        if R == 0:
+            return (zeros(rows_h, d) if need_dh else None), (zeros(V, d) if need_dw else None), None, None, None, None
+        h_live, Wc, a2, idx, cst, h_slot, w_slot = ctx.saved_tensors
+        g32 = g.to(torch.float32).reshape(1).contiguous()   # a device scalar: the kernels read it, the host never does
+        gslot = torch.empty(1, device=dev, dtype=torch.int32)
+        call("care_head_grad_scale", ptr(g32), gslot.data_ptr())
+        ksd, ksv = _ceil64(d), _ceil64(V)
+        dh_live = torch.empty(R, d, device=dev, dtype=torch.float32) if need_dh else None
+        plan = [(a, b, _x3_slabs(V, d, b - a)) for a, b in head_chunks(R)]
+        terms = sum(s for _, _, s in plan)
+        dw_terms, at = None, 0
+        for a, b, slabs in plan:
+            # one buffer of the size of W's pieces or of the chunk's at a time: W's pieces in either orientation are split per
+            # chunk (a sweep of W - microseconds against the chunk's products) and dropped before the next buffer is taken
+            n = b - a
+            w3 = torch.empty(V, 3 * ksd, device=dev, dtype=torch.float16)
+            call("care_split_pieces", ptr(Wc), Wc.stride(0), V, d, 0, 1, ksd, ptr(w3), 3, w_slot.data_ptr())
+            dl2 = torch.empty(n, 2 * ksv, device=dev, dtype=torch.float16)
+            call("care_gemm_tile_split3_head_grad", ptr(a2[a:]), ptr(w3), h_slot.data_ptr(), w_slot.data_ptr(), ptr(idx[2][a:]),
+                 ptr(cst[0][a:]), ptr(cst[1][a:]), ptr(g32), gslot.data_ptr(), eps, ptr(dl2), n, V, ksd)
+            del w3
+            if need_dh:   # dh = dl W: W^T as the [d, V] operand, pieces with the forward's |max| of W
+                wt3 = torch.empty(d, 3 * ksv, device=dev, dtype=torch.float16)
+                call("care_split_pieces", ptr(Wc), Wc.stride(0), d, V, 1, 1, ksv, ptr(wt3), 3, w_slot.data_ptr())
+                call("care_gemm_tile_split3_scaled", ptr(dl2), ptr(wt3), None, ptr(dh_live[a:]), d, n, d, ksv, gslot.data_ptr(),
+                     w_slot.data_ptr(), 1)
+                del wt3
+            if need_dw:   # dW = dl^T h: the reduction runs over the chunk's rows, in slabs when the output has few tiles
+                ksr = _ceil64((n + slabs - 1) // slabs)
+                dlt = torch.empty(slabs * V, 2 * ksr, device=dev, dtype=torch.float16)
+                call("care_pieces_transpose", ptr(dl2), n, V, ksv, slabs, ksr, ptr(dlt))
+                del dl2
+                if dw_terms is None:   # (taken here, not up front: W's pieces and dl's are gone by now - the peak stays at the pieces)
+                    dw_terms = torch.empty(terms * V, d, device=dev, dtype=torch.float32)
+                ht3 = torch.empty(slabs * d, 3 * ksr, device=dev, dtype=torch.float16)
+                call("care_split_pieces", ptr(h_live[a:]), d, d, n, 1, slabs, ksr, ptr(ht3), 3, h_slot.data_ptr())
+                call("care_gemm_tile_split3_scaled", ptr(dlt), ptr(ht3), None, ptr(dw_terms[at * V:]), d, V, d, ksr, gslot.data_ptr(),
+                     h_slot.data_ptr(), slabs)
+                at += slabs
+                del dlt, ht3
+        dW = None
+        if need_dw:   # slabs and chunks added in order: one grouping, the same bits every time
+            dW = dw_terms if terms == 1 else _strided_sum(dw_terms, V, terms, 1, V)
+        dhid = None
+        if need_dh:
+            dhid = zeros(rows_h, d)
+            call("care_scatter_rows", ptr(dh_live), d * 4, ptr(dhid), d * 4, ptr(idx[0]), R, d * 4)
+        return dhid, dW, None, None, None, None
 
 
 class _NoisyOrBCE(torch.autograd.Function):
@@ -170,10 +350,18 @@ class LanguageGeneration(CritBase):
         assert logits.dim() == 3 and labels.dim() == 2 and logits.size(0) == labels.size(0)
         if logits.size(1) != labels.size(1) + 1:      # crit_lang.py:49-52
             assert logits.size(1) == labels.size(1), (tuple(logits.shape), tuple(labels.shape))
+        live = None
+        if isinstance(logits, DeferredLogits) and labels.device.type == "cpu":   # a loader's batch: counted before the copy
+            live = int(((labels > 0) & (labels < logits.size(2))).sum())
         labels32 = labels.to(device=logits.device, dtype=torch.int32).contiguous()
         if self.acc is None:
             self.acc = torch.zeros(5, device=logits.device, dtype=torch.float64)
-        loss, pred, counts = _LangLoss.apply(_rows_f32(logits), labels32, self.label_smoothing, self.acc)
+        if isinstance(logits, DeferredLogits):   # set_fused_head(True): head + loss over the live label positions
+            hidden = logits.hidden
+            loss, pred, counts = _HeadLoss.apply(hidden.reshape(hidden.shape[0] * hidden.shape[1], hidden.shape[2]), logits.weight,
+                                                 labels32, self.label_smoothing, self.acc, live)
+        else:
+            loss, pred, counts = _LangLoss.apply(_rows_f32(logits), labels32, self.label_smoothing, self.acc)
         self.last_pred, self.last_counts = pred, counts   # arg-max tokens [N, t]; (hits, words, bad labels) of this call
         return loss
 

@@ -69,6 +69,10 @@ struct TArgs {
   // split products of PRE-SCALED operands (care_gemm_tile_split3_scaled): the |max| bit patterns the two operands' power-of-two
   // scales were derived from (care_absmax); the epilogue multiplies the accumulators by 1 / (scale_a scale_b).  NULL: no scaling.
   const unsigned* amax_a; const unsigned* amax_b;
+  // the training head fused with the language loss (EPI_HEAD_STATS / EPI_HEAD_GRAD; labels = the live rows' labels):
+  // psx: per (row, part) the sum of the part's logits; rmax / lsum: a row's max and log sum exp(x - max) from the forward;
+  // g: the upstream gradient (a device scalar), gbits: the |max| slot of the gradient's pieces (|g|); dl: the pieces [M, 2 ks_out]
+  float* psx; const float* rmax; const float* lsum; const float* g; const unsigned* gbits; float eps; _Float16* dl; int ks_out;
 };
 
 // The power of two that brings a tensor's largest magnitude into [2^14, 2^15) - the top of fp16's range, so that the LOW piece
@@ -81,7 +85,7 @@ __device__ __forceinline__ int pow2_scale_exp(unsigned bits) {
 }
 __device__ __forceinline__ float pow2_of(int e) { return __builtin_bit_cast(float, (unsigned)(127 + e) << 23); }
 
-enum { EPI_STORE = 0, EPI_ARGMAX = 1, EPI_ARGMAX_LAB = 2, EPI_BEAM = 3 };
+enum { EPI_STORE = 0, EPI_ARGMAX = 1, EPI_ARGMAX_LAB = 2, EPI_BEAM = 3, EPI_HEAD_STATS = 4, EPI_HEAD_GRAD = 5 };
 
 // Block -> output tile.  Blocks are dealt to the 8 XCDs round robin and in order, so the 32 workgroups an XCD runs at a
 // time are 32 CONSECUTIVE numbers of its run (bijective for any grid size); inside a run the tiles go in bands of
@@ -235,6 +239,88 @@ __device__ __forceinline__ void tile_epilogue(const TArgs& p, f32x4 (&acc)[MT][4
           for (int j = 0; j < 16; ++j)
             if (j < nvalid) dst[j] = v[j];
         }
+      }
+    }
+  } else if constexpr (EPI == EPI_HEAD_STATS) {
+    // the forward of the training head fused with its loss: the statistics of the arg-max epilogue below on x = acc * alpha
+    // (the operands are pre-scaled: back to the true magnitude by the exact power of two EPI_STORE applies, before anything
+    // else - the logits are bit for bit those care_gemm_tile_split3_scaled would store), + the label's logit and the sum of
+    // the part's logits (label smoothing: lse - mean x).  expf, not __expf: these sums are a loss, not a ranking.
+    const float alpha = pow2_of(-pow2_scale_exp(*p.amax_a)) * pow2_of(-pow2_scale_exp(*p.amax_b));
+    const int part = (col0 - fg * 16) >> 6;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int row = row0 + m * 16 + fr;
+      const int lab = p.labels[min(row, p.M - 1)];
+      float x[16];
+      float best = -INFINITY, lv = -INFINITY, sx = 0.0f;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int col = col0 + 4 * n + j;
+          const float v = acc[m][n][j] * alpha;
+          x[4 * n + j] = v;
+          if (col < p.N) {
+            if (v > best) { best = v; bi = col; }  // columns ascend: the first maximum is kept
+            sx += v;
+            if (col == lab) lv = v;
+          }
+        }
+#pragma unroll
+      for (int o = 16; o < 64; o <<= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+      }
+      float s = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 16; ++j)
+        if (col0 + j < p.N) s += expf(x[j] - best);
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      sx += __shfl_xor(sx, 16, 64);
+      sx += __shfl_xor(sx, 32, 64);
+      lv = fmaxf(lv, __shfl_xor(lv, 16, 64));
+      lv = fmaxf(lv, __shfl_xor(lv, 32, 64));
+      if (fg == 0 && row < p.M && part < p.parts) {
+        const int64_t o = (int64_t)row * p.parts + part;
+        p.pmax[o] = best; p.pidx[o] = bi; p.psum[o] = s; p.plab[o] = lv; p.psx[o] = sx;
+      }
+    }
+  } else if constexpr (EPI == EPI_HEAD_GRAD) {
+    // the backward: the same product again (same pieces, same K order: the forward's x bit for bit), the gradient of the
+    // logits per element - care_lang_loss_bwd's expression - and its scaled fp16 pieces hi | lo straight into the A-operand
+    // layout [M, 2 ks_out] of the two gradient products: a lane's 16 consecutive columns are 32 bytes of each piece.
+    // |dl| <= |g|, so the pieces' power-of-two scale comes from |g| (gbits): nothing sweeps the gradient for its maximum.
+    const float alpha = pow2_of(-pow2_scale_exp(*p.amax_a)) * pow2_of(-pow2_scale_exp(*p.amax_b));
+    const float gg = *p.g, sg = pow2_of(pow2_scale_exp(*p.gbits)), sub = p.eps / (float)p.N, hot = 1.0f - p.eps;
+    typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+      const int row = row0 + m * 16 + fr, rc = min(row, p.M - 1);
+      const int lab = p.labels[rc];
+      const float mx = p.rmax[rc], ls = p.lsum[rc];
+      f16x8 hi[2], lo[2];
+#pragma unroll
+      for (int n = 0; n < 4; ++n)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int col = col0 + 4 * n + j;
+          const float xv = acc[m][n][j] * alpha;
+          float d = gg * ((expf((xv - mx) - ls) - sub) - (col == lab ? hot : 0.0f));
+          d = col < p.N ? d * sg : 0.0f;  // columns N .. ks_out - 1: the zero padding of the K dimension of dl W
+          const _Float16 h = (_Float16)d;
+          hi[n >> 1][4 * (n & 1) + j] = h;
+          lo[n >> 1][4 * (n & 1) + j] = (_Float16)(d - (float)h);
+        }
+      if (row < p.M && col0 < p.ks_out) {  // ks_out % 64 == 0, col0 % 16 == 0: the 16 columns lie inside the piece whole
+        _Float16* o = p.dl + (int64_t)row * 2 * p.ks_out + col0;
+        *reinterpret_cast<f16x8*>(o) = hi[0];
+        *reinterpret_cast<f16x8*>(o + 8) = hi[1];
+        *reinterpret_cast<f16x8*>(o + p.ks_out) = lo[0];
+        *reinterpret_cast<f16x8*>(o + p.ks_out + 8) = lo[1];
       }
     }
   } else {
@@ -752,6 +838,43 @@ extern "C" int care_gemm_tile_split3_argmax(const void* A2, const void* W3, floa
   hipStream_t st = (hipStream_t)stream;
   return pick_cfg(M, N, 3 * K) == 4412 ? launch_tile<4, 4, 1, 2, EPI_ARGMAX, true>(p, st) : launch_tile<2, 2, 1, 2, EPI_ARGMAX, true>(p, st);
 }
+// The training head fused with the language loss (include/care_hip.h; care_amd/criterion.py, _HeadLoss): the split product of
+// care_gemm_tile_split3_scaled with the logits kept in the accumulators - forward statistics, then the gradient's pieces.
+// The tile shapes of care_gemm_tile_split3_scaled (a row's results do not depend on the shape: every accumulator sees the
+// same K steps in the same order).
+extern "C" int care_gemm_tile_split3_head_stats(const void* A2, const void* W3, const void* amax_a, const void* amax_b,
+                                                const int32_t* labels, float* pmax, int32_t* pidx, float* psum, float* plab,
+                                                float* psx, int M, int N, int K, void* stream) {
+  int rc = tile_check(A2, 2 * (int64_t)K, W3, M, N, K);
+  if (rc) return rc;
+  if (!amax_a || !amax_b || !labels || !pmax || !pidx || !psum || !plab || !psx) return CARE_EINVAL;
+  TArgs p{};
+  split3_args(p, A2, W3, M, N, K);
+  p.amax_a = reinterpret_cast<const unsigned*>(amax_a); p.amax_b = reinterpret_cast<const unsigned*>(amax_b);
+  p.labels = labels; p.pmax = pmax; p.pidx = pidx; p.psum = psum; p.plab = plab; p.psx = psx; p.parts = care_argmax_parts_tile(N);
+  hipStream_t st = (hipStream_t)stream;
+  const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+  return t256 >= 192 ? launch_tile<4, 4, 1, 2, EPI_HEAD_STATS, true>(p, st) : launch_tile<2, 2, 1, 2, EPI_HEAD_STATS, true>(p, st);
+}
+
+extern "C" int care_gemm_tile_split3_head_grad(const void* A2, const void* W3, const void* amax_a, const void* amax_b,
+                                               const int32_t* labels, const float* rmax, const float* lsum, const float* g,
+                                               const void* gbits, float eps, void* out, int M, int N, int K, void* stream) {
+  int rc = tile_check(A2, 2 * (int64_t)K, W3, M, N, K);
+  if (rc) return rc;
+  if (!amax_a || !amax_b || !labels || !rmax || !lsum || !g || !gbits || !out) return CARE_EINVAL;
+  if (!care_aligned16(out)) return CARE_EALIGN;
+  if (!(eps >= 0.f && eps <= 1.f)) return CARE_ESHAPE;
+  TArgs p{};
+  split3_args(p, A2, W3, M, N, K);
+  p.amax_a = reinterpret_cast<const unsigned*>(amax_a); p.amax_b = reinterpret_cast<const unsigned*>(amax_b);
+  p.labels = labels; p.rmax = rmax; p.lsum = lsum; p.g = g; p.gbits = reinterpret_cast<const unsigned*>(gbits); p.eps = eps;
+  p.dl = reinterpret_cast<_Float16*>(out); p.ks_out = (N + 63) / 64 * 64;
+  hipStream_t st = (hipStream_t)stream;
+  const long t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+  return t256 >= 192 ? launch_tile<4, 4, 1, 2, EPI_HEAD_GRAD, true>(p, st) : launch_tile<2, 2, 1, 2, EPI_HEAD_GRAD, true>(p, st);
+}
+
 extern "C" int care_argmax_parts_tile(int N) { return N > 0 ? (N + 63) / 64 : CARE_EINVAL; }
 
 extern "C" int care_gemm_tile_beam(const void* A, int64_t lda, const void* W, float* pmax, float* psum, float* gmax, int M,

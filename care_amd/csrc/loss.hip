@@ -291,6 +291,14 @@ extern "C" int care_lang_loss_fwd(const float* logits, int64_t ld, int64_t seq_s
   return care_launch_status();
 }
 
+extern "C" int care_lang_loss_reduce(const float* row_loss, const float* logp, const int32_t* pred, const int32_t* labels, int V,
+                                     int rows, float* sums, int32_t* counts, double* acc, void* stream) {
+  if (!row_loss || !logp || !pred || !labels || !sums || !counts || rows <= 0 || V <= 0) return CARE_EINVAL;
+  if (acc && ((uintptr_t)acc & 7u)) return CARE_EALIGN;
+  hipLaunchKernelGGL(lang_loss_reduce_kernel, dim3(1), dim3(1024), 0, LST, row_loss, logp, pred, labels, V, rows, sums, counts, acc);
+  return care_launch_status();
+}
+
 extern "C" int care_lang_loss_bwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V,
                                   const int32_t* labels, const float* rmax, const float* lsum, float eps, const float* g,
                                   float* dlogits, int64_t ldd, int64_t dseq_stride, int seq_rows, int rows, void* stream) {

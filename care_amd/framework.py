@@ -297,6 +297,7 @@ class TransformerSeq2Seq(nn.Module):
         self._engine_stamp = None
         self._compute_dtype = opt.get("care_compute_dtype") or os.environ.get("CARE_AMD_DTYPE", "fp32")
         self._compute_dtype = {"half": "fp16", "16bit": "fp16"}.get(self._compute_dtype, self._compute_dtype)
+        self._fused_head = os.environ.get("CARE_TRAIN_FUSED_HEAD", "0").strip().lower() in ("1", "true", "on", "yes")
 
     # -- initialisation: same distributions as models/Framework.py:115-134
     def _init_weights(self):
@@ -341,6 +342,19 @@ class TransformerSeq2Seq(nn.Module):
     @property
     def compute_dtype(self) -> str:
         return self._compute_dtype
+
+    def set_fused_head(self, on: bool) -> "TransformerSeq2Seq":
+        """Training mode only (care_amd/training.py reads it): True - the vocabulary head is not run by forward(); `logits` is a
+        care_amd.criterion.DeferredLogits (the hidden states + the head's weight) and LanguageGeneration runs the head fused
+        with its loss over the live label positions, the [N, t, V] logits and their gradient never in memory.
+        Default: off (the environment variable CARE_TRAIN_FUSED_HEAD=1 turns it on for models built afterwards); with it off
+        every launch and result of training mode is what it was.  Eval mode does not read it."""
+        self._fused_head = bool(on)
+        return self
+
+    @property
+    def fused_head(self) -> bool:
+        return bool(getattr(self, "_fused_head", False))
 
     def engine(self) -> HipEngine:
         if self.training:

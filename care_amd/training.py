@@ -20,6 +20,9 @@ forward AND backward are HIP kernels behind the C ABI (include/care_hip.h):
   * embeddings: care_gather_rows / care_scatter_add_rows, care_add_pos_sem; the concept head: care_concept_finish /
     care_concept_bwd; mean pooling: care_group_mean / care_bcast_rows.
 
+  * the vocabulary head, optionally (model.set_fused_head(True), default off): not run here at all - `logits` is a
+    criterion.DeferredLogits and LanguageGeneration runs projection + loss + backward over the live label rows (criterion._HeadLoss);
+
 torch itself only moves data (transposes, zero padding to the kernels' K % 32, cat / slicing) and runs the
 autograd engine (which also sums the gradients of a tensor with several consumers).  fp32 arithmetic; the module's
 own nn.Parameters are the operands, so `loss.backward()` fills their `.grad` and any torch optimiser steps them.
@@ -594,8 +597,12 @@ def training_forward(model, batch: Dict[str, Any], **kwargs) -> Dict[str, Any]:
     if pre_ln:  # Decoder/Transformer.py:80-81,233-234: the decoder's final LayerNorm, in front of the head
         x = _AddLN.apply(x, None, P["decoder.LayerNorm.weight"], P["decoder.LayerNorm.bias"], eps)
     hidden = drop(x, p_hid)  # Decoder/Transformer.py:236-237
-    logits = _Linear.apply(hidden, P["cls_head.tgt_word_prj.weight"], None)
     out["hidden_states"] = hidden.view(N, t, d)
-    out["logits"] = logits.view(N, t, -1)
+    if getattr(model, "_fused_head", False):   # set_fused_head(True): the head runs inside the criterion, over the live label rows
+        from .criterion import DeferredLogits
+        out["logits"] = DeferredLogits(out["hidden_states"], P["cls_head.tgt_word_prj.weight"])
+    else:
+        logits = _Linear.apply(hidden, P["cls_head.tgt_word_prj.weight"], None)
+        out["logits"] = logits.view(N, t, -1)
     out["schedule_sampling_prob"] = 0
     return out

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CARE_ABI_VERSION 23
+#define CARE_ABI_VERSION 24
 
 enum { CARE_F32 = 0, CARE_BF16 = 1 };
 enum { CARE_ACT_NONE = 0, CARE_ACT_RELU = 1, CARE_ACT_GELU = 2 };
@@ -670,6 +670,58 @@ int care_noisy_or_bce_fwd(const float* preds, int64_t ldp, const float* labels, 
                           float* sums, double* acc, int B, int K, void* stream);
 int care_noisy_or_bce_bwd(const float* preds, int64_t ldp, const float* labels, int64_t ldl, const float* denom, const float* g,
                           float* dpreds, int64_t ldd, int B, int K, void* stream);
+
+/*
+ * The training head fused with the language loss (models/Head.py:26-32: logits = hidden tgt_word_prj^T; misc/Crit/crit_lang.py:49-71:
+ * the [N, t + 1] against [N, t] rule, log_softmax, NLLLoss, the label-smoothing mean, the PAD mask; care_amd/criterion.py,
+ * _HeadLoss).  The vocabulary projection, the loss and its backward over the LIVE label positions only (label in [1, V)); no
+ * [rows, V] fp32 tensor is written at any point.  The head's products are split products of pre-scaled fp16 hi / lo pieces
+ * (care_absmax -> care_split_pieces -> the LDS-tiled kernel with F16 operands), whatever the other layers use.
+ *
+ * care_head_live_rows (Head.py:26-32 is applied to these rows only; crit_lang.py:49-52,63-66): the ordered (ascending)
+ *   compaction of the n_seq * t label positions with 0 < label < V: for the i-th live position r = s * t + p
+ *     idx_h[i] = s * seq_rows + p (its row of the hidden states [n_seq, seq_rows >= t, d]), idx_l[i] = r, lab_c[i] = label;
+ *   counts[0] = live positions, counts[1] = labels outside [0, V).  The three index arrays hold n_seq * t entries (the
+ *   entries from counts[0] on are left as they are).  One workgroup; PAD and out-of-range labels are never used as an index.
+ * care_gemm_tile_split3_head_stats (Head.py:26-32 + crit_lang.py:57-60): x = (A2 W3^T) / (scale_a scale_b) as
+ *   care_gemm_tile_split3_scaled computes it (the accumulators times the exact power of two BEFORE any statistic), never
+ *   stored; per (row, 64-column part) - parts = care_argmax_parts_tile(N), arrays [M, parts] -
+ *     pmax = max x, pidx = FIRST arg-max column, psum = sum exp(x - pmax), plab = x[labels[row]] (-inf when the label is not
+ *     in the part), psx = sum x over the part's columns < N.  labels [M]: the live rows' labels (lab_c).
+ * care_head_loss_finish (crit_lang.py:57-71): merges the parts of live row i < R into rmax = max x, lsum = log sum exp(x - max)
+ *   (kept apart for the backward, as care_lang_loss_fwd keeps them), lse, logp = (x[y] - rmax) - lsum, pred (lowest index on
+ *   ties) and row_loss = (1 - eps) (-logp) + eps (lse - sum x / V); written at position idx_l[i] of the per-position arrays
+ *   of care_lang_loss_fwd's layout, rmax / lsum also at i of rmax_c / lsum_c [R].  One wave per row, a fixed order.
+ * care_lang_loss_reduce (crit_lang.py:63-71,83-103): care_lang_loss_fwd's ordered one-workgroup reduction on its own - sums,
+ *   counts and acc as described there, over per-position arrays filled by care_head_loss_finish (dead positions are
+ *   skipped by their label).  No floating-point atomics: two calls give the same bits.
+ * care_head_grad_scale: *slot = the bit pattern of |*g| (one thread).  |dl| <= |g| for every element of the gradient of
+ *   the logits, so the power-of-two scale of its pieces comes from the device scalar g - there is no |max| sweep.
+ * care_gemm_tile_split3_head_grad (the backward of crit_lang.py:57-71 to the logits of Head.py:26-32): recomputes x from the
+ *   same pieces in the same K order and writes, for row r < M and column c < ks = ceil64(N),
+ *     dl = g (exp((x - rmax[r]) - lsum[r]) - eps / N - (1 - eps) [c == labels[r]])   (0 for N <= c < ks)
+ *   as the fp16 pieces hi | lo of dl * 2^e(gbits) into out [M, 2 ks] - the A operand of care_gemm_tile_split3_scaled with
+ *   amax_a = gbits.  rmax / lsum / labels [M] (compact).  out 16-byte aligned.
+ * care_pieces_transpose: fp16 pieces [R, 2 ks_v] (hi | lo of [R, ks_v]) -> slab-major pieces of the transpose,
+ *   out [slabs][V, 2 ks_r]: out[s][v][q ks_r + k] = src[s ks_r + k][q ks_v + v] (zero for s ks_r + k >= R), q = 0, 1 - the A
+ *   operand of dW = dl^T h (Head.py:26-32 backward).  fp16 to fp16 through 64 x 64 LDS tiles; ks_v, ks_r multiples of 64,
+ *   V <= ks_v, slabs ks_r >= R.
+ */
+int care_head_live_rows(const int32_t* labels, int n_seq, int t, int seq_rows, int V, int32_t* idx_h, int32_t* idx_l,
+                        int32_t* lab_c, int32_t* counts, void* stream);
+int care_gemm_tile_split3_head_stats(const void* A2, const void* W3, const void* amax_a, const void* amax_b, const int32_t* labels,
+                                     float* pmax, int32_t* pidx, float* psum, float* plab, float* psx, int M, int N, int K,
+                                     void* stream);
+int care_head_loss_finish(const float* pmax, const int32_t* pidx, const float* psum, const float* plab, const float* psx, int parts,
+                          const int32_t* lab_c, const int32_t* idx_l, int V, float eps, int R, float* lse, float* rmax,
+                          float* lsum, float* logp, int32_t* pred, float* row_loss, float* rmax_c, float* lsum_c, void* stream);
+int care_lang_loss_reduce(const float* row_loss, const float* logp, const int32_t* pred, const int32_t* labels, int V, int rows,
+                          float* sums, int32_t* counts, double* acc, void* stream);
+int care_head_grad_scale(const float* g, void* slot, void* stream);
+int care_gemm_tile_split3_head_grad(const void* A2, const void* W3, const void* amax_a, const void* amax_b, const int32_t* labels,
+                                    const float* rmax, const float* lsum, const float* g, const void* gbits, float eps, void* out,
+                                    int M, int N, int K, void* stream);
+int care_pieces_transpose(const void* src, int R, int V, int ks_v, int slabs, int ks_r, void* out, void* stream);
 
 /*
  * care_decode_resident: the whole greedy decode of a SMALL batch (1 .. a few hundred caption rows) as ONE launch.
