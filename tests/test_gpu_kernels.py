@@ -1268,3 +1268,179 @@ def test_f32_gemm_of_few_tiles_is_bit_identical_to_the_lds_tiled_kernel(M, N, K,
                                b.view(torch.int32 if b.dtype == torch.float32 else torch.int16))   # (NaN padding included)
     ref = A.double() @ W.double().t()
     assert (outs["1"][2].double() - ref).abs().max().item() < 2e-4
+
+
+# ------------------------------------------------------------------ teacher-forced scoring: label logit + partials
+_label_w = {}
+
+
+def _label_weight(N, K):
+    """The [N, K] bf16 vocabulary matrix of the care_label_logits cases, made once per K."""
+    if K not in _label_w:
+        _label_w[K] = _rand(N, K, seed=131, scale=0.05).to(torch.bfloat16).contiguous()
+    return _label_w[K]
+
+
+@pytest.mark.parametrize("pad", [0, 8])
+@pytest.mark.parametrize("K", [8, 512, 520, 1024])
+@pytest.mark.parametrize("rows", [1, 5, 1030])
+def test_label_logits(rows, K, pad):
+    """care_label_logits: out[r] = A[r] . W[col[r]], a wave per row, 8 elements per lane and pass (K = 8: one lane; 512: one
+    full pass; 520: a pass and one lane; 1024: two passes), against the float64 dot product of the same bf16 operands - the
+    operands are exact, only the order of the fp32 sum differs: the fp32 bar of this file."""
+    N = 10547
+    buf = torch.full((rows, K + pad), float("nan"), device=DEV, dtype=torch.bfloat16)
+    A = buf[:, :K]
+    A.copy_(_rand(rows, K, seed=130))
+    W = _label_weight(N, K)
+    col = torch.randint(1, N - 1, (rows,), generator=torch.Generator().manual_seed(rows + K), dtype=torch.int32).to(DEV)
+    col[0] = 0
+    col[rows - 1] = N - 1
+    out = torch.full((rows + 4,), float("nan"), device=DEV)
+    _call("care_label_logits", _p(buf), K + pad, _p(W), _p(col), _p(out), rows, N, K)
+    ref = (A.double() * W[col.long()].double()).sum(1)
+    torch.cuda.synchronize()
+    err = (out[:rows].double() - ref).abs().max().item()
+    print("care_label_logits rows %d K %d lda %d: max error %.3g / 1e-4" % (rows, K, K + pad, err))
+    assert err < 1e-4
+    assert torch.isnan(out[rows:]).all()
+
+
+def test_label_logits_clamps_columns_and_rejects_bad_arguments():
+    """A column outside [0, N) - a PAD or stray label - reads row 0 or N - 1 of W, never outside it."""
+    from care_amd import _lib
+
+    N, K = 10547, 512
+    A = _rand(4, K, seed=132).to(torch.bfloat16)
+    A[2], A[3] = A[0], A[1]
+    W = _label_weight(N, K)
+    col = torch.tensor([-1, N + 5, 0, N - 1], dtype=torch.int32, device=DEV)
+    out = torch.full((4,), float("nan"), device=DEV)
+    _call("care_label_logits", _p(A), K, _p(W), _p(col), _p(out), 4, N, K)
+    ref = (A.double() * W[[0, N - 1, 0, N - 1]].double()).sum(1)
+    torch.cuda.synchronize()
+    assert (out.double() - ref).abs().max().item() < 1e-4
+    assert torch.equal(out[:2].view(torch.int32), out[2:].view(torch.int32))
+    A12 = _rand(4, 16, seed=133).to(torch.bfloat16)
+    with pytest.raises(_lib.CareHipError, match="EALIGN"):
+        _call("care_label_logits", _p(A12), 16, _p(W), _p(col), _p(out), 4, N, 12)
+    with pytest.raises(_lib.CareHipError, match="EALIGN"):
+        _call("care_label_logits", _p(A), K + 4, _p(W), _p(col), _p(out), 4, N, K)
+    with pytest.raises(_lib.CareHipError, match="EINVAL"):
+        _call("care_label_logits", None, K, _p(W), _p(col), _p(out), 4, N, K)
+    with pytest.raises(_lib.CareHipError, match="EINVAL"):
+        _call("care_label_logits", _p(A), K, _p(W), _p(col), _p(out), 0, N, K)
+
+
+@pytest.mark.parametrize("M", [3, 200, 1030])
+def test_label_scoring_from_partials_and_label_logits(M):
+    """The pair the engine's teacher-forced scoring runs (care_label_logits + care_score_partials_lab on partials computed
+    without labels), at test_fused_label_scoring's shapes and bars.  The label logit and the row maximum come from different
+    summation orders: where the label is a dominant arg-max the log-probability may rise above zero by no more than 1e-4."""
+    from care_amd import _lib
+
+    N, K = 10547, 512
+    W = (_rand(N, K, seed=41, scale=0.05)).to(torch.bfloat16).contiguous()
+    A = _rand(M, K, seed=40).to(torch.bfloat16)
+    labels = torch.randint(0, N, (M,), dtype=torch.int32).to(DEV)
+    labels[0] = N - 1
+    A[1] = (W[int(labels[1])].float() * 40).to(torch.bfloat16)  # row 1: its label dominates the row
+    parts = _lib.argmax_parts(N, M, True)
+    pm, ps = (torch.full((M, parts), float("nan"), device=DEV) for _ in range(2))
+    pi = torch.full((M, parts), -7, device=DEV, dtype=torch.int32)
+    _call("care_gemm_argmax_bf16", _p(A), K, 1, _p(W), _p(pm), _p(pi), _p(ps), None, None, M, N, K)
+    lab = torch.full((M,), float("nan"), device=DEV)
+    _call("care_label_logits", _p(A), K, _p(W), _p(labels), _p(lab), M, N, K)
+    logp, pred = torch.full((M,), float("nan"), device=DEV), torch.full((M,), -7, device=DEV, dtype=torch.int32)
+    _call("care_score_partials_lab", _p(pm), _p(pi), _p(ps), parts, _p(lab), _p(logp), _p(pred), M)
+    logits = A.double() @ W.double().t()
+    ref = torch.log_softmax(logits, dim=1).gather(1, labels.long().unsqueeze(1)).squeeze(1)
+    torch.cuda.synchronize()
+    err = (logp.double() - ref).abs().max().item()
+    print("care_score_partials_lab M %d: max error %.3g / 2e-3, dominant label logp %.3g" % (M, err, float(logp[1])))
+    assert err < 2e-3
+    top2 = logits.topk(2, dim=1)
+    safe = (top2[0][:, 0] - top2[0][:, 1]) > 1e-3
+    assert torch.equal(pred[safe].long(), top2[1][:, 0][safe])
+    assert bool(safe[1]) and int(pred[1]) == int(labels[1]) and float(ref[1]) > -1e-6
+    assert float(logp[1]) <= 1e-4
+
+
+@pytest.mark.parametrize("parts", [1, 64, 65, 166])
+def test_score_partials_lab_on_hand_made_partials(parts):
+    """care_score_partials_lab alone: parts below, at and above a wave's 64 lanes; equal maxima in two parts (the lower
+    column wins, whichever part holds it); a part without a finite logit (-inf, sum 0) - against the float64 formula."""
+    rows = 9
+    g = torch.Generator().manual_seed(parts)
+    pm = torch.randn(rows, parts, generator=g) * 3
+    ps = 1 + 63 * torch.rand(rows, parts, generator=g)
+    pi = torch.stack([torch.randperm(10547, generator=g)[:parts] for _ in range(rows)]).to(torch.int32)
+    if parts > 1:
+        for r in range(rows):
+            a, b = (r * 7) % parts, (r * 7 + 1 + r % (parts - 1)) % parts   # two different parts
+            pm[r, a] = pm[r, b] = pm[r].max() + 0.5
+            if parts > 2:
+                c = next(x for x in range(parts) if x not in (a, b))
+                pm[r, c], ps[r, c], pi[r, c] = float("-inf"), 0.0, 0   # would win every tie-break if it counted
+    lab = pm.max(1)[0] - torch.rand(rows, generator=g) * 5
+    pm, ps, pi, lab = pm.to(DEV), ps.to(DEV), pi.to(DEV), lab.to(DEV)
+    logp, pred = torch.full((rows + 3,), float("nan"), device=DEV), torch.full((rows + 3,), -7, device=DEV, dtype=torch.int32)
+    _call("care_score_partials_lab", _p(pm), _p(pi), _p(ps), parts, _p(lab), _p(logp), _p(pred), rows)
+    mx = pm.double().max(1, keepdim=True)[0]
+    lse = (ps.double() * torch.exp(pm.double() - mx)).sum(1).log() + mx.squeeze(1)
+    want = torch.where(pm == mx.float(), pi, torch.full_like(pi, 2 ** 31 - 1)).min(1)[0]
+    torch.cuda.synchronize()
+    err = (logp[:rows].double() - (lab.double() - lse)).abs().max().item()
+    print("care_score_partials_lab parts %d: max error %.3g / 1e-4" % (parts, err))
+    assert err < 1e-4
+    assert torch.equal(pred[:rows], want)
+    assert torch.isnan(logp[rows:]).all() and bool((pred[rows:] == -7).all())
+
+
+@pytest.mark.parametrize("M,K", [(1, 1024), (129, 512), (1000, 768)])
+def test_gemm_tile_split3_argmax(M, K):
+    """The fused vocabulary arg-max on split (fp32-grade) products - the greedy head of the fp16x3 mode: per 64-column part
+    (max, lowest arg-max, sum exp), reduced by care_score_partials_lab, against the fp64 product of the fp32 operands; exact
+    ties between far-apart columns and inside the ragged last tile go to the lower column.  Its epilogue reads the same
+    accumulators as care_gemm_tile_split3's store (same tile shape, same K steps): the part maxima are the stored logits' bits."""
+    from care_amd import _lib
+
+    N = 10547
+    W = _rand(N, K, seed=82, scale=0.05)
+    W[N // 2 + 5] = W[11]
+    W[N - 1] = W[N - 2]
+    A = _rand(M, K, seed=81)
+    A[0] = W[11] * 10
+    A[M - 1] = W[N - 2] * 10
+    W3 = torch.empty(N, 3 * K, device=DEV, dtype=torch.float16)
+    _call("care_split3_weight", _p(W), _p(W3), N, K)
+    A2 = torch.empty(M, 2 * K, device=DEV, dtype=torch.float16)
+    _call("care_split2_act", _p(A), K, _p(A2), M, K)
+    parts = _lib.load().care_argmax_parts_tile(N)
+    pm, ps = torch.full((M, parts), float("nan"), device=DEV), torch.full((M, parts), float("nan"), device=DEV)
+    pi = torch.full((M, parts), -7, device=DEV, dtype=torch.int32)
+    _call("care_gemm_tile_split3_argmax", _p(A2), _p(W3), _p(pm), _p(pi), _p(ps), M, N, K)
+    out = torch.full((M, parts * 64), float("-inf"), device=DEV)
+    _call("care_gemm_tile_split3", _p(A2), _p(W3), None, _p(out), out.stride(0), 0, None, 0, 0, N, M, N, K, 0)
+    labels = torch.randint(0, N, (M,), device=DEV, dtype=torch.int32)
+    lab = out.gather(1, labels.long().unsqueeze(1)).squeeze(1).contiguous()
+    logp, pred = torch.full((M,), float("nan"), device=DEV), torch.full((M,), -7, device=DEV, dtype=torch.int32)
+    _call("care_score_partials_lab", _p(pm), _p(pi), _p(ps), parts, _p(lab), _p(logp), _p(pred), M)
+    ref = A.double() @ W.double().t()
+    torch.cuda.synchronize()
+    assert (out[:, :N].double() - ref).abs().max().item() < 2e-5 and bool((out[:, N:] == float("-inf")).all())
+    blocks = out.view(M, parts, 64)
+    bmax = blocks.max(2)[0]
+    cols = torch.arange(parts * 64, device=DEV, dtype=torch.int32).view(1, parts, 64).expand(M, -1, -1)
+    bidx = torch.where(blocks == bmax.unsqueeze(2), cols, torch.full_like(cols, 2 ** 31 - 1)).min(2)[0]
+    assert torch.equal(pm, bmax) and torch.equal(pi, bidx)   # bit-equal: the same accumulators
+    bsum = torch.exp(blocks.double() - bmax.double().unsqueeze(2)).sum(2)
+    assert ((ps.double() - bsum).abs() / bsum).max().item() < 1e-5   # (__expf: a few ulp per term)
+    top2 = ref.topk(2, dim=1)
+    safe = (top2[0][:, 0] - top2[0][:, 1]) > 1e-3
+    assert torch.equal(pred[safe].long(), top2[1][:, 0][safe])
+    assert int(pred[M - 1]) == N - 2 and (M == 1 or int(pred[0]) == 11)   # ties: the lower column
+    lse = lab.double() - logp.double()
+    err = (lse - torch.logsumexp(ref, dim=1)).abs().max().item()
+    print("care_gemm_tile_split3_argmax M %d K %d: log-sum-exp max error %.3g / 1.2e-4" % (M, K, err))
+    assert err < 2e-5 + 1e-4

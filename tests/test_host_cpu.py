@@ -116,6 +116,21 @@ def test_library_is_bound_to_its_sources(tmp_path, monkeypatch):
     assert build.embedded_hash(str(junk)) is None
 
 
+def test_every_compute_entry_point_is_named_by_a_test():
+    """Every entry point include/care_hip.h declares - but the bench's clock probe and the getters / switches in _lib.PLAIN,
+    which compute nothing - is called by name somewhere in tests/: none is held by whole-model runs alone."""
+    import glob
+
+    from care_amd import _lib
+
+    header = open(os.path.join(ROOT, "include", "care_hip.h")).read()
+    declared = set(re.findall(r"^(?:int|int64_t|void|const char\*)\s+(care_\w+)\s*\(", header, re.M))
+    assert len(declared) >= 80
+    text = "\n".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "tests", "*.py")) if p != os.path.abspath(__file__))
+    named = set(re.findall(r"\bcare_\w+", text))
+    assert sorted(declared - set(_lib.PLAIN) - {"care_timestamp"} - named) == []
+
+
 def test_abi_library_exports_every_declared_symbol():
     """The .so loads and exports exactly the entry points include/care_hip.h declares."""
     import ctypes
