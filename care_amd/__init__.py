@@ -4,9 +4,13 @@ Public seam (mirrors the reference's two factories):
     from care_amd import get_framework, get_translator
 and, for training, the reference's criteria behind `misc.Crit`'s interface (care_amd/criterion.py):
     from care_amd import get_criterion
+and the optimiser step behind `Wrapper.configure_optimizers`' interface (care_amd/optim.py):
+    from care_amd import configure_optimizers, Adam
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
 from .criterion import Criterion, LanguageGeneration, NoisyOrMIL, get_criterion  # noqa: F401
+from .optim import Adam, configure_optimizers, filter_weight_decay  # noqa: F401
 
-__all__ = ["get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL"]
+__all__ = ["get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+           "Adam", "configure_optimizers", "filter_weight_decay"]

@@ -12,7 +12,7 @@ import torch
 CARE_F32, CARE_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 ACT_CODES = {"linear": ACT_NONE, "relu": ACT_RELU, "gelu": ACT_GELU}
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _ERRORS = {-1: "CARE_EINVAL (null pointer / bad size)", -2: "CARE_EALIGN (alignment)",
            -3: "CARE_ESHAPE (unsupported shape)", -4: "CARE_EDTYPE (unknown dtype/activation)"}
@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("CARE_HIP_LIB") or os.path.join(os.path.dirname(os.pat
 VARIANT_H16 = {"": "bf16", "f16": "fp16"}
 
 # name -> argtypes, in the exact order of include/care_hip.h
-_P, _I, _L, _F, _U = c_void_p, c_int, c_int64, c_float, c_uint64
+_P, _I, _L, _F, _U, _D = c_void_p, c_int, c_int64, c_float, c_uint64, ctypes.c_double
 SIGNATURES = {
     "care_gemm": [_P, _L, _P, _I, _P, _P, _L, _I, _P, _L, _I, _I, _I, _I, _I, _I, _P],
     "care_split3_weight": [_P, _P, _I, _I, _P],
@@ -110,6 +110,8 @@ SIGNATURES = {
     "care_expand_index": [_P, _I, _I, _P, _P],
     "care_remap_rows": [_P, _L, _P, _I, _P],
     "care_beam_advance": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "care_grad_sqnorm": [_P, _I, _P, _P, _P],
+    "care_adam_step": [_P, _I, _D, _D, _D, _D, _P, _D, _P],
 }
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
@@ -122,7 +124,8 @@ PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_
          "care_decode_chain_beam_scratch": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
          "care_decode_resident_debug": (None, [c_int, c_int]),
          "care_resident_set_fenced": (None, [c_int]), "care_resident_fenced": (c_int, []),
-         "care_gemm_kn_splits": (c_int, [c_int, c_int, c_int])}
+         "care_gemm_kn_splits": (c_int, [c_int, c_int, c_int]),
+         "care_grad_sqnorm_partials": (c_int, [c_int64])}
 
 
 class ResidentAttn(ctypes.Structure):
@@ -137,6 +140,13 @@ class ResidentLayer(ctypes.Structure):
     _fields_ = [("qkv_w", c_void_p), ("qkv_b", c_void_p), ("o_w", c_void_p), ("o_b", c_void_p), ("ln_g", c_void_p), ("ln_b", c_void_p),
                 ("self_kv", c_void_p), ("att", ResidentAttn * 2), ("n_att", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("ffn_g", c_void_p), ("ffn_b", c_void_p)]
+
+
+class OptTensor(ctypes.Structure):
+    """care_opt_tensor (include/care_hip.h)."""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64),
+                ("step_size", c_float), ("weight_decay", c_float)]
+
 
 _libs = {}
 

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CARE_ABI_VERSION 24
+#define CARE_ABI_VERSION 25
 
 enum { CARE_F32 = 0, CARE_BF16 = 1 };
 enum { CARE_ACT_NONE = 0, CARE_ACT_RELU = 1, CARE_ACT_GELU = 2 };
@@ -722,6 +722,49 @@ int care_gemm_tile_split3_head_grad(const void* A2, const void* W3, const void* 
                                     const float* rmax, const float* lsum, const float* g, const void* gbits, float eps, void* out,
                                     int M, int N, int K, void* stream);
 int care_pieces_transpose(const void* src, int R, int V, int ks_v, int slabs, int ks_r, void* out, void* stream);
+
+/*
+ * The optimiser step (models/Wrapper.py:316-386: configure_optimizers builds torch.optim.Adam; train.py:128 / opts.py:145:
+ * Lightning's gradient_clip_val runs clip_grad_norm_ before it; misc/utils.py:282-304: the weight-decay groups; care_amd/optim.py).
+ * One sweep for the norm of all gradients and one for the update of all parameters, whatever the number of tensors.  fp32 in
+ * both library variants.
+ *
+ * care_opt_tensor: one parameter tensor - p, g, m (exp_avg), v (exp_avg_sq): fp32, contiguous, n elements each, 4-byte
+ *   aligned; step_size = lr / (1 - beta1^t) and weight_decay are the tensor's parameter group's (0 = no decay).  `tensors`
+ *   is a HOST array: the descriptors travel in the kernel arguments, CARE_OPT_PACK tensors per launch, so a step uploads
+ *   nothing and a list of any length is ceil(count / CARE_OPT_PACK) launches.
+ * care_grad_sqnorm (torch.nn.utils.clip_grad_norm_, norm type 2, as Lightning's gradient_clip_val calls it, train.py:128):
+ *   *norm (DEVICE float) = the L2 norm of all g together.  Every tensor is cut into chunks of 1024 elements; workgroup b of
+ *   care_grad_sqnorm_partials(total) takes a contiguous range of the chunks, adds squares in fp32 per lane and the lanes in
+ *   double in a fixed order into partials[b] (DEVICE doubles, 8-byte aligned, care_grad_sqnorm_partials(total) of them,
+ *   total = sum n); one workgroup adds the partials in index order and takes the square root.  No floating-point atomics:
+ *   the same inputs give the same bits.  p, m, v are not touched (and may be anything non-NULL).  count == 0: *norm = 0.
+ * care_adam_step (torch.optim.Adam's single-tensor arithmetic, torch 2.10 optim/adam.py _single_tensor_adam with amsgrad =
+ *   maximize = False, as Wrapper.py:316-386 builds it, with clip_grad_norm_'s coefficient folded in): per element, in fp32,
+ *     c  = norm ? min(1, max_norm / (*norm + 1e-6)) : 1      (read from the DEVICE scalar; a NaN norm gives a NaN c)
+ *     g' = c g;  if (weight_decay != 0) g' += weight_decay p
+ *     m += (g' - m) (1 - beta1);   v = beta2 v + (1 - beta2) g' g'
+ *     p -= step_size m / (sqrt(v) / bias2_sqrt + eps)         (bias2_sqrt = sqrt(1 - beta2^t), by the host in double)
+ *   g is read and never written: .grad stays unscaled after a clipped step (clip_grad_norm_ scales it in place).  beta1,
+ *   beta2, eps, bias2_sqrt and max_norm are doubles: 1 - beta is taken in double before it is rounded to fp32, as torch
+ *   takes it.  One pass: 16-byte loads and stores in every chunk whose four pointers are 16-byte aligned (a 0..3-element
+ *   scalar tail in a tensor's last chunk), scalar ones in the others; nothing at or beyond element n is written.
+ *   count == 0 is a no-op that returns 0.
+ * Both: a NULL pointer in a descriptor, NULL tensors with count > 0, count < 0 or n < 0 -> CARE_EINVAL; a pointer that is
+ *   not 4-byte aligned (partials: 8-byte) -> CARE_EALIGN; more than 2^31 - 1 chunks in one launch -> CARE_ESHAPE; all before
+ *   anything is launched.
+ */
+#define CARE_OPT_PACK 64
+typedef struct care_opt_tensor {
+  float* p; const float* g; float* m; float* v;
+  int64_t n;
+  float step_size;
+  float weight_decay;
+} care_opt_tensor;
+int care_grad_sqnorm_partials(int64_t total);
+int care_grad_sqnorm(const care_opt_tensor* tensors, int count, double* partials, float* norm, void* stream);
+int care_adam_step(const care_opt_tensor* tensors, int count, double beta1, double beta2, double eps, double bias2_sqrt,
+                   const float* norm, double max_norm, void* stream);
 
 /*
  * care_decode_resident: the whole greedy decode of a SMALL batch (1 .. a few hundred caption rows) as ONE launch.
