@@ -112,6 +112,9 @@ SIGNATURES = {
     "care_beam_advance": [_P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "care_grad_sqnorm": [_P, _I, _P, _P, _P],
     "care_adam_step": [_P, _I, _D, _D, _D, _D, _P, _D, _P],
+    "care_ema_step": [_P, _I, _D, _D, _P],
+    "care_mse_fwd": [_P, _P, _L, _P, _P, _P],
+    "care_mse_bwd": [_P, _P, _L, _P, _P, _P],
 }
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
@@ -125,7 +128,8 @@ PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_
          "care_decode_resident_debug": (None, [c_int, c_int]),
          "care_resident_set_fenced": (None, [c_int]), "care_resident_fenced": (c_int, []),
          "care_gemm_kn_splits": (c_int, [c_int, c_int, c_int]),
-         "care_grad_sqnorm_partials": (c_int, [c_int64])}
+         "care_grad_sqnorm_partials": (c_int, [c_int64]),
+         "care_mse_partials": (c_int, [c_int64])}
 
 
 class ResidentAttn(ctypes.Structure):
@@ -146,6 +150,11 @@ class OptTensor(ctypes.Structure):
     """care_opt_tensor (include/care_hip.h)."""
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64),
                 ("step_size", c_float), ("weight_decay", c_float)]
+
+
+class EmaTensor(ctypes.Structure):
+    """care_ema_tensor (include/care_hip.h)."""
+    _fields_ = [("t", c_void_p), ("s", c_void_p), ("n", c_int64)]
 
 
 _libs = {}

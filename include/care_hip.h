@@ -767,6 +767,45 @@ int care_adam_step(const care_opt_tensor* tensors, int count, double beta1, doub
                    const float* norm, double max_norm, void* stream);
 
 /*
+ * The mean-teacher step (models/Wrapper.py:550-614: InterplayModel - a student trained by the criterion plus a
+ * distillation term towards a teacher that is the exponential moving average of the student; opts.py:253-255: ema_weight,
+ * distillation_weight, eval_model; care_amd/interplay.py).  fp32 in both library variants.
+ *
+ * care_ema_tensor: one parameter pair - t (the teacher's, written) and s (the student's, read and never written): fp32,
+ *   contiguous, n elements each, 4-byte aligned.  `tensors` is a HOST array: the descriptors travel in the kernel arguments,
+ *   CARE_EMA_PACK tensors per launch, so an update uploads nothing and a list of any length is ceil(count / CARE_EMA_PACK)
+ *   launches.
+ * care_ema_step (Wrapper.py:574-581: torch._foreach_mul_(teacher, w); torch._foreach_add_(teacher, torch._foreach_mul(student,
+ *   1 - w))): per element, in fp32 with every operation rounded on its own (no fused multiply-add),
+ *     t = fl(fl(t (float)w) + fl(s (float)one_minus_w))
+ *   - the bits of the three torch calls.  one_minus_w is the caller's double 1 - w; both are narrowed to float by the host.
+ *   One pass: 16-byte loads and stores in every 1024-element chunk whose two pointers are 16-byte aligned (a 0..3-element
+ *   scalar tail in a tensor's last chunk), scalar ones in the others; nothing at or beyond element n is written.  An empty
+ *   tensor owns no chunk; count == 0 is a no-op that returns 0.  A NULL pointer in a descriptor, NULL tensors with
+ *   count > 0, count < 0, n < 0 or t == s -> CARE_EINVAL; a pointer that is not 4-byte aligned -> CARE_EALIGN; more than
+ *   2^31 - 1 chunks in one launch -> CARE_ESHAPE; all before anything is launched.
+ * care_mse_fwd (Wrapper.py:565:((student_logits - teacher_logits) ** 2).mean()): *loss (DEVICE float) =
+ *   (float)(sum (a_i - b_i)^2 / n) - the difference in fp32 as torch takes it, its square and every sum in double.  a and b
+ *   are cut into chunks of 1024 elements; workgroup w of care_mse_partials(n) takes a contiguous range of the chunks and
+ *   writes partials[w] (DEVICE doubles, 8-byte aligned, care_mse_partials(n) of them), one workgroup adds the partials in
+ *   index order.  No floating-point atomics: the same inputs give the same bits; grid and partial count depend on n only.
+ *   a and b may start at any 4-byte phase: 0..3 scalars are peeled up to the 16-byte boundary when both have the same
+ *   phase, everything moves as scalars when they differ.
+ * care_mse_bwd: da_i = fl(fl(a_i - b_i) c), c = (float)(2 (double)*g / (double)n) with g the upstream gradient, a DEVICE
+ *   scalar read by the kernel.  The difference is recomputed from the operands; da (n floats) may be a or b itself.
+ * Both: a NULL pointer or n <= 0 -> CARE_EINVAL; a pointer that is not 4-byte aligned (partials: 8-byte) -> CARE_EALIGN.
+ */
+#define CARE_EMA_PACK 128
+typedef struct care_ema_tensor {
+  float* t; const float* s;
+  int64_t n;
+} care_ema_tensor;
+int care_ema_step(const care_ema_tensor* tensors, int count, double w, double one_minus_w, void* stream);
+int care_mse_partials(int64_t n);
+int care_mse_fwd(const float* a, const float* b, int64_t n, double* partials, float* loss, void* stream);
+int care_mse_bwd(const float* a, const float* b, int64_t n, const float* g, float* da, void* stream);
+
+/*
  * care_decode_resident: the whole greedy decode of a SMALL batch (1 .. a few hundred caption rows) as ONE launch.
  *   Replaces the step loop of Translator.translate_batch with beam_size 1 (models/Translator.py:77-143: embedding,
  *   models/Decoder.py + models/components/Layers.py:157-228 per layer, Head.py:26-32, the top-1 of Beam.advance, and
