@@ -61,6 +61,18 @@ constexpr int LAT_D = 512;
 constexpr int CH_KEYS = 16;
 constexpr int CH_BYTES = CH_KEYS * LAT_D * 2;  // 16 KiB
 
+// Lazy online softmax (all three kernels): how far a chunk's maximum may rise above the reference maximum before the
+// reference moves and the accumulators are rescaled.  Until then the probabilities are exp(s - m_ref) <= exp(LAT_RESCALE),
+// and they are cast to the 16-bit type for the P . mem MFMA - so exp(LAT_RESCALE) must be finite there, with headroom.
+// bf16 has fp32's exponent range: exp(16) ~ 9e6.  IEEE half ends at 65504 = e^11.09: exp(8) ~ 3e3 (a threshold of 16
+// sent +inf into the MFMA for jumps between 11.09 and 16, and inf or NaN - inf x 0 - out of it).  One definition for the
+// three copies: the few-rows form stays bit-identical to the streaming one.
+#ifdef CARE_H16_FP16
+constexpr float LAT_RESCALE = 8.0f;
+#else
+constexpr float LAT_RESCALE = 16.0f;
+#endif
+
 struct LatArgs {
   const bf16_t* qt; int64_t ldq;      // [rows][heads][512], row stride in elements
   const bf16_t* mem; int64_t mem_bs, mem_rs;  // memory block of clip b at mem + b*mem_bs, key stride mem_rs
@@ -250,13 +262,14 @@ __global__ __launch_bounds__(WAVES * 64, 1) void attention_latent_kernel(LatArgs
 
       // ---- online softmax over the keys of each head, with a LAZY reference maximum: the
       // exponentials are taken against m_ref, which only moves (and only then are the 128
-      // accumulator registers rescaled) when a chunk's maximum exceeds it by more than 16 -
-      // softmax is shift-invariant, exp(16) ~ 9e6 is harmless in fp32/bf16, and in the common case
-      // the accumulators are touched by nothing but the MFMAs (they stay in AGPRs).
+      // accumulator registers rescaled) when a chunk's maximum exceeds it by more than LAT_RESCALE
+      // (16 in the bf16 library, 8 in the half one) - softmax is shift-invariant, exp(LAT_RESCALE)
+      // is finite in fp32 and in the library's 16-bit type, and in the common case the
+      // accumulators are touched by nothing but the MFMAs (they stay in AGPRs).
       float cm = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
       cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
       cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-      if (__any(cm > m_ref + 16.0f)) {  // wave-uniform; always taken on a row's first chunk (m_ref = -inf)
+      if (__any(cm > m_ref + LAT_RESCALE)) {  // wave-uniform; always taken on a row's first chunk (m_ref = -inf)
         const float m_new = fmaxf(m_ref, cm);
         const float alpha = __expf(m_ref - m_new);  // exp(-inf) = 0 on the first chunk
         m_ref = m_new;
@@ -525,7 +538,7 @@ __global__ __launch_bounds__(64 * NW, 1) void attention_latentN_kernel(LatArgs p
       float cm = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
       cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
       cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-      if (__any(cm > m_ref + 16.0f)) {
+      if (__any(cm > m_ref + LAT_RESCALE)) {
         const float m_new = fmaxf(m_ref, cm);
         const float alpha = __expf(m_ref - m_new);
         m_ref = m_new;
@@ -734,7 +747,7 @@ __global__ __launch_bounds__(64, 1) void attention_latent_few_kernel(LatArgs p) 
     float cm = fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3]));
     cm = fmaxf(cm, __shfl_xor(cm, 16, 64));
     cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
-    if (__any(cm > m_ref + 16.0f)) {
+    if (__any(cm > m_ref + LAT_RESCALE)) {
       const float m_new = fmaxf(m_ref, cm);
       const float alpha = __expf(m_ref - m_new);
       m_ref = m_new;

@@ -3,6 +3,11 @@
 bf16 kernels are compared with the same math on bf16-ROUNDED operands accumulated in
 fp32/fp64 (that is what the MFMA computes), so the tolerance only has to cover summation
 order: 2e-3 absolute on O(1..30) outputs.  fp32 kernels: 1e-4 at K <= 2048.
+
+This file runs on libcare_hip.so, the library whose 16-bit type is bfloat16 (the two `variant`-parametrised loader-wave
+tests excepted).  tests/test_gpu_kernels_f16.py runs every kernel family that uses the 16-bit type on BOTH libraries -
+libcare_hip.so and libcare_hip_f16.so (IEEE half) - side by side, and holds the cases that only half's format makes hard:
+exponent range in the lazy softmax, conversion semantics, subnormal operands.
 """
 import math
 
