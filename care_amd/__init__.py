@@ -8,12 +8,16 @@ and the optimiser step behind `Wrapper.configure_optimizers`' interface (care_am
     from care_amd import configure_optimizers, Adam
 and the mean-teacher step of `--wrapper InterplayModel` (models/Wrapper.py:550-614; care_amd/interplay.py):
     from care_amd import InterplayStep, distillation_mse, ema_update
+and the `r` modality retrieved on device from a bank of caption embeddings (pretreatment/clip_retrieval.py; care_amd/retrieval.py):
+    from care_amd import CaptionBank, attach_retrieval
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
 from .criterion import Criterion, LanguageGeneration, NoisyOrMIL, get_criterion  # noqa: F401
 from .optim import Adam, configure_optimizers, filter_weight_decay  # noqa: F401
 from .interplay import InterplayStep, distillation_mse, ema_update  # noqa: F401
+from .retrieval import CaptionBank, attach_retrieval  # noqa: F401
 
 __all__ = ["get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
-           "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update"]
+           "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
+           "CaptionBank", "attach_retrieval"]

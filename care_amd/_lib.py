@@ -115,6 +115,10 @@ SIGNATURES = {
     "care_ema_step": [_P, _I, _D, _D, _P],
     "care_mse_fwd": [_P, _P, _L, _P, _P, _P],
     "care_mse_bwd": [_P, _P, _L, _P, _P, _P],
+    "care_l2_normalize_rows": [_P, _P, _I, _I, _P],
+    "care_retrieval_query": [_P, _P, _I, _I, _I, _P],
+    "care_retrieval_topk": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
+    "care_retrieval_gather": [_P, _I, _I, _P, _I, _P, _P],
 }
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
@@ -129,7 +133,8 @@ PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_
          "care_resident_set_fenced": (None, [c_int]), "care_resident_fenced": (c_int, []),
          "care_gemm_kn_splits": (c_int, [c_int, c_int, c_int]),
          "care_grad_sqnorm_partials": (c_int, [c_int64]),
-         "care_mse_partials": (c_int, [c_int64])}
+         "care_mse_partials": (c_int, [c_int64]),
+         "care_retrieval_scratch": (c_int64, [c_int, c_int, c_int])}
 
 
 class ResidentAttn(ctypes.Structure):

@@ -4,7 +4,9 @@ Restates the evaluation branch of `VideoOnlyDataset` (dataloader.py:142-190,232-
 modality a table `video<id> -> [60, dim]` (HDF5 in the reference; any Mapping here, h5py is
 absent from this image), 28 of the 60 rows picked by `get_uniform_ids_from_k_snippets`
 (misc/utils.py:311-317) for `load_feats_type == 0`, retrieval features = the first
-`retrieval_topk` rows (dataloader.py:808-814), missing videos = zeros.  `FeaturePrefetcher`
+`retrieval_topk` rows (dataloader.py:808-814), missing videos = zeros.  (Those rows need not come from a table written
+offline: `care_amd.retrieval.attach_retrieval` retrieves them on device from a `CaptionBank` and the batch's `i` tensor.)
+`FeaturePrefetcher`
 adds what the reference lacks: pinned double-buffered host staging with the H2D copy on a
 side stream, so an 8-GPU node is not input-bound (301 KB per clip over PCIe).
 """

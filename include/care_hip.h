@@ -806,6 +806,44 @@ int care_mse_fwd(const float* a, const float* b, int64_t n, double* partials, fl
 int care_mse_bwd(const float* a, const float* b, int64_t n, const float* g, float* da, void* stream);
 
 /*
+ * Caption retrieval (pretreatment/clip_retrieval.py:47-83 `run`, :175-176 the two normalisations of `load`, :305-321 the
+ * per-video call and the rows that are stored; dataloader.py:808-814 takes the first `retrieval_topk` of them as the `r`
+ * modality; care_amd/retrieval.py).  Builds that modality on device from a bank of caption embeddings.  fp32 in both
+ * library variants; nothing here synchronises with the host.
+ *
+ * care_l2_normalize_rows (:176): y [M, D] = x [M, D] with every row divided by its L2 norm (sum of squares in a fixed order).
+ * care_retrieval_query (:105-110, :175): q [B, D] = the mean over the n frames of frames [B, n, D] (summed in frame order,
+ *   divided by n), divided by its L2 norm.
+ * care_retrieval_topk (:47-83): per row b of q [B, D] the topk columns j of bank [M, D] (unit rows) with the largest
+ *   q_b . bank_j among the ELIGIBLE ones, ordered by (score descending, j ascending).  Scores are exact f32
+ *   (v_mfma_f32_16x16x4_f32) with ONE summation order for every (row, column) - k in blocks of 16, within a block
+ *   k = 4 g + i taken i-major - whatever B, the row's place in the batch or the column's place in a tile, so bit-identical
+ *   bank rows score bit-identically against a query and the tie rule decides.  The [B, M] scores never exist: a scan keeps
+ *   the maximum over the eligible columns of every 16-column group, the topk groups of a row are re-scored with the same
+ *   summation order and ranked.
+ *   Eligibility of column j for row b, with [start_b, end_b) the row's own range (`info`; start == end == NULL: none):
+ *   j outside [start_b, end_b) and - when first / prev are given (`unique`: first[j] the lowest member of j's group of equal
+ *   captions, prev[j] the previous member or -1) - prev[j] < 0 or (first[j] >= start_b and prev[j] < end_b): j is the lowest
+ *   member of its group outside the own range.  All of these are in the numbering of the scanned bank; orig (optional, [M],
+ *   ascending: the `sampled_indices` of --ratio) only renames the ids that are written.
+ *   Out: ids int64 [B, topk] (-1 past count), scores fp32 [B, topk] (-inf past count), count int32 [B] = min(topk,
+ *   eligible columns).  scratch: care_retrieval_scratch(B, M, topk) bytes (< 0: unsupported shape), 16-byte aligned.
+ * care_retrieval_gather (:318-321): out [n, De] = table[ids[i]] (the UN-normalised embeddings, possibly of another width:
+ *   --arch_f); a row of zeros where ids[i] is negative or not below `rows`.
+ * All: D / De a multiple of 16 up to 1024, 1 <= topk <= 128, 1 <= M <= 2^31 - 64, B >= 1 (n >= 1) or CARE_ESHAPE; a NULL
+ *   pointer, one of start / end or of first / prev without the other, or a scratch that is too small -> CARE_EINVAL; a
+ *   pointer that is not 16-byte aligned (the int32 / int64 arrays and count: their element size) -> CARE_EALIGN; all before
+ *   anything is launched.
+ */
+int care_l2_normalize_rows(const float* x, float* y, int M, int D, void* stream);
+int care_retrieval_query(const float* frames, float* q, int B, int n, int D, void* stream);
+int64_t care_retrieval_scratch(int B, int M, int topk);
+int care_retrieval_topk(const float* q, const float* bank, int B, int M, int D, int topk, const int32_t* start,
+                        const int32_t* end, const int32_t* first, const int32_t* prev, const int32_t* orig,
+                        int64_t* ids, float* scores, int32_t* count, void* scratch, int64_t scratch_bytes, void* stream);
+int care_retrieval_gather(const float* table, int rows, int De, const int64_t* ids, int n, float* out, void* stream);
+
+/*
  * care_decode_resident: the whole greedy decode of a SMALL batch (1 .. a few hundred caption rows) as ONE launch.
  *   Replaces the step loop of Translator.translate_batch with beam_size 1 (models/Translator.py:77-143: embedding,
  *   models/Decoder.py + models/components/Layers.py:157-228 per layer, Head.py:26-32, the top-1 of Beam.advance, and
