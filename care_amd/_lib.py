@@ -46,6 +46,8 @@ SIGNATURES = {
     "care_greedy_update": [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "care_greedy_update_embed": [_P, _P, _P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _F,
                                  _P, _P, _L, _I, _P],
+    "care_sample_logits": [_P, _L, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "care_sample_accum": [_P, _P, _P, _I, _P],
     "care_add_ln": [_P, _L, _P, _L, _P, _P, _P, _F, _P, _P, _L, _I, _I, _I, _I, _I, _I, _L, _P],
     "care_gemm_ln": [_P, _L, _I, _P, _P, _P, _L, _P, _P, _P, _F, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
     "care_gemm_ln_packed": [_P, _L, _I, _P, _P, _P, _L, _P, _P, _F, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],

@@ -33,13 +33,14 @@ from .engine_beam import BeamMixin
 from .engine_decode import DecodeMixin
 from .engine_encode import EncodeMixin
 from .engine_resident import ResidentMixin
+from .engine_sample import SampleMixin
 from .engine_util import _LaneOutputs, device_props  # noqa: F401
 
 
 _CAPTURE_LOCK = threading.Lock()   # hipGraph captures are serialised across engines and threads (HipEngine._replay)
 
 
-class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
+class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin, SampleMixin):
     def __init__(self, opt: dict, dtype: str = "fp32"):
         if dtype not in ("fp32", "bf16", "fp16", "fp16x3"):
             raise ValueError("compute dtype must be 'fp32', 'bf16', 'fp16' or 'fp16x3', got {!r}".format(dtype))
@@ -389,7 +390,7 @@ class HipEngine(EncodeMixin, DecodeMixin, ResidentMixin, BeamMixin):
     # Captured graphs per kind (first element of the key).  The whole-pass kinds are keyed on the caller's feature
     # buffers, the segment kinds on (buffer set, first step, rows): a loader with ragged last batches, or a caller
     # that allocates fresh feature tensors for every batch, must not grow them without limit.
-    GRAPH_CAPS = {"greedy": 8, "beam": 8, "gseg0": 8, "bseg0": 8, "gseg": 96, "bseg": 96, "tf": 8, "gres": 8}
+    GRAPH_CAPS = {"greedy": 8, "beam": 8, "gseg0": 8, "bseg0": 8, "gseg": 96, "bseg": 96, "tf": 8, "gres": 8, "sample": 8}
 
     def _graph_get(self, key):
         entry = self._graphs.get(key)

@@ -119,6 +119,48 @@ class Translator_ARFormer(object):
                 done = self._finish(prev)
             yield done
 
+    # ------------------------------------------------------------------ sampled decoding
+    def sample_batch(self, models: List[torch.nn.Module], batch: dict, n_samples: int = 1, temperature: float = 1.0,
+                     top_k: int = 0, top_p: float = 1.0, seed: int = None, with_logq: bool = False, sample_ids=None,
+                     use_graph: bool = True):
+        """`n_samples` captions per clip DRAWN from the model's distribution (include/care_hip.h,
+        care_sample_logits): logits / temperature, the top_k best tokens (0: all), of those the smallest prefix whose
+        probability reaches top_p (1: all), one Gumbel-max draw per step keyed by (seed, sample_ids[clip] n_samples + draw,
+        step) - the same seed gives the same captions, seed None takes one from torch's generator (torch.manual_seed).
+        Returns `(batch_hyps, batch_scores)` in translate_batch's format: batch_hyps[i] the n_samples token lists of clip i
+        in draw order (no BOS, EOS when emitted), batch_scores[i][j] the MODEL's log-probability of caption j - temperature
+        1, no filter: what a pseudo-label or a sequence-level objective weighs - over length ** beam_alpha.  with_logq: a
+        third list, the un-normalised sum of the log-probabilities under the distribution actually drawn from (what an
+        importance weight needs).  One model in eval mode on the device; there is no CPU form."""
+        from .engine_sample import check_sample_args
+        check_sample_args(n_samples, temperature, top_k, top_p)
+        if len(models) != 1:
+            raise ValueError("sample_batch draws from ONE model, got {} (ensembles are outside sampled decoding)".format(len(models)))
+        if getattr(models[0], "training", False):
+            raise ValueError("sample_batch needs the model in eval mode: call .eval() (training mode runs under autograd)")
+        feats = batch["feats"]
+        feats = list(feats[0] if isinstance(feats[0], list) else feats)
+        if not all(isinstance(f, torch.Tensor) and f.is_cuda for f in feats):
+            raise ValueError("sample_batch needs the features on the device: CPU tensors have no fallback path")
+        with self._device_of(models), self._turn(models), torch.no_grad():
+            engine, feats = self._engine_and_feats(models, batch)
+            _, fed, length, score, score_q = engine.translate_sample(feats, n_samples, temperature, top_k, top_p, seed=seed,
+                                                                     use_graph=use_graph, sample_ids=sample_ids)
+            event, (length, score, score_q, fed) = self._fetch([length, score, score_q, fed])
+            if event is not None:
+                event.synchronize()
+            flat = []
+            for _ in self._token_lists(flat, fed[:, 1:], length):
+                pass
+            norm = self._norm(score, length).tolist()
+            n = n_samples
+            hyps = [flat[i: i + n] for i in range(0, len(flat), n)]
+            scores = [norm[i: i + n] for i in range(0, len(norm), n)]
+            if with_logq:
+                q = score_q.astype(np.float64).tolist()
+                return hyps, scores, [q[i: i + n] for i in range(0, len(q), n)]
+            return hyps, scores
+
     # ------------------------------------------------------------------ launch: the device pass + one D2H copy
     _ABORTED = ("the resident decode timed out at a hand-off: its workgroups never became resident together (another "
                 "long-running kernel holds CUs?); set CARE_RESIDENT_MAX_ROWS=0 / CARE_RESIDENT_BEAM_MAX_ROWS=0")

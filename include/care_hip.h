@@ -234,6 +234,37 @@ int care_greedy_update_embed(const float* pmax, const int32_t* pidx, const float
                              void* out_bf16, int64_t ldo, int d, void* stream);
 
 /*
+ * care_sample_logits: draw one token per row from the row's logits - temperature, top-k, nucleus (top-p) - and hand it to
+ *   care_greedy_update / care_greedy_update_embed through their parts = 1 contract (csrc/sample.hip).  No reference
+ *   counterpart: the reference decodes by beam search only.
+ *   logits fp32 [rows, ld], columns V .. ld - 1 are never read; -inf entries carry probability 0 and are never chosen.
+ *   params: a 24-byte DEVICE block, 16-byte aligned, read by the kernel - so a captured hipGraph replays with a new seed or
+ *   new settings: { uint64 seed; float inv_temperature; float top_p; int32 top_k; int32 reserved }.
+ *   Per row, x = logits[row, 0 : V]:
+ *     1. s_i = x_i * inv_temperature;
+ *     2. top-k (off for top_k <= 0 or >= V): the top_k first entries by (s descending, index ascending);
+ *     3. top-p (off for top_p >= 1): of those, in that order, with q_i = exp(s_i - m) / Z over them, entry j stays when the
+ *        summed q of the entries before it is < top_p - the smallest prefix whose mass reaches top_p, never empty;
+ *     4. tok = argmax over the kept set of s_i + g_i, ties to the lower index (Gumbel-max: stateless, a row is checkable on
+ *        its own): g_i = -logf(-logf(u_i)), u_i = (2 k + 1) 2^-24 with k the top 23 bits of h(h(seed, (key << 16) | t), i),
+ *        h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin the splitmix64 finaliser, key = row_key[row] (NULL: the row
+ *        index), t the decoder step (1-based).  u lies in (0, 1) and is exact in fp32; g <= 16.64, so a Gumbel tail of
+ *        probability 6e-8 per entry is cut off.
+ *   Out, all [rows]: pmax = x[tok], pidx = tok, psum = sum over ALL V columns of exp(x_i - x[tok]) (so -log psum is the
+ *   MODEL's log-probability of tok at temperature 1); logq (optional) = s_tok - logsumexp over the kept set of s, the
+ *   log-probability under the distribution sampled from; nkept (optional) = the size of the kept set.
+ *   Deterministic (fixed reduction orders, no floating-point atomics); a row's result depends on its logits, key, t and
+ *   params alone.  rows == 0 is a no-op.  CARE_EINVAL: rows < 0, V < 1, ld < V, t < 1, a NULL logits / params / pmax / pidx /
+ *   psum; CARE_EALIGN: params not 16-byte aligned.
+ * care_sample_accum: score_q[r] += logq[r] for every row with finished[r] == 0 - the running sum of logq of a sampled
+ *   decode, issued in front of the step's care_greedy_update, which sets `finished`.
+ */
+int care_sample_logits(const float* logits, int64_t ld, int V, int rows, const int32_t* row_key, int t,
+                       const void* params, float* pmax, int32_t* pidx, float* psum, float* logq, int32_t* nkept,
+                       void* stream);
+int care_sample_accum(const float* logq, const int32_t* finished, float* score_q, int rows, void* stream);
+
+/*
  * care_add_ln: out = LayerNorm(x + res) * gamma + beta, row-wise over d columns.
  *   Replaces nn.LayerNorm after the Embedder Linear (models/Encoder.py:167) and the
  *   post-LN residual epilogues of MultiHeadAttention / PositionwiseFeedForward
