@@ -4,35 +4,19 @@
 // library variants.
 //
 // All three are streaming kernels: 12 B per element for the average (read t, s, write t), 8 B for the loss (read a, b),
-// 12 B for its gradient (read a, b, write da) and a handful of VALU operations.  The average follows optim.hip: the
-// tensor list reaches the kernel BY VALUE in its arguments (ema_pack.h: 128 descriptors a launch), every tensor is cut
-// into chunks of 1024 elements, a grid of at most 2048 workgroups of 256 splits the launch's chunks into contiguous ranges
-// of equal length (+-1), and a chunk whose two pointers are 16-byte aligned moves as one float4 per lane and array.  The
-// loss kernels cut ONE array the same way; its base may sit at any 4-byte phase (a row of logits is V = 10547 floats),
-// so 0..3 scalars are peeled up to the 16-byte boundary and the chunks start there.
-//
-// No floating-point atomics: a workgroup's sum goes to a partial of its own (double), a second one-workgroup kernel adds
-// the partials in index order.
+// 12 B for its gradient (read a, b, write da) and a handful of VALU operations.  The tensor list of the average reaches its
+// kernel BY VALUE in the arguments (sweep.h: CARE_EMA_PACK descriptors a launch); the cut into chunks, the walk, the lanes
+// of a chunk and the sums are sweep.h's.  The loss kernels cut ONE array the same way; its base may sit at any 4-byte
+// phase (a row of logits is V = 10547 floats), so 0..3 scalars are peeled up to the 16-byte boundary and the chunks
+// start there.
 #include "care_common.h"
-#include "ema_pack.h"
+#include "sweep.h"
 
 namespace {
 
 #define IST ((hipStream_t)stream)
-constexpr int IT = 256;
-constexpr int IGRID = 2048;
-static_assert(CARE_EMA_CHUNK == 4 * IT, "a chunk is one float4 per lane");
+constexpr int IT = CARE_SWEEP_THREADS;
 static_assert(sizeof(care_ema_tensor) == 24 && sizeof(care_ema_pack) <= 3840, "the pack and the scalars fit the 4-KB argument block");
-
-// the tensor that owns chunk ch of the pack: the last i with start[i] <= ch (an empty tensor never is)
-__device__ __forceinline__ int owner_of(const care_ema_pack& pk, int ch) {
-  int lo = 0, hi = pk.count;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (pk.start[mid] <= ch) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 // torch._foreach_mul_(t, w); torch._foreach_add_(t, torch._foreach_mul(s, 1 - w)): three roundings, never an FMA.
 // (__fmul_rn / __fadd_rn are plain operators in their header, which the compiler contracts by default: the operators
@@ -46,42 +30,27 @@ __device__ __forceinline__ float ema_one(float t, float s, float w, float omw) {
 
 __global__ __launch_bounds__(IT) void ema_step_kernel(const care_ema_pack pk, int chunks, float w, float omw) {
   const int tid = threadIdx.x;
-  const int c0 = (int)((int64_t)chunks * blockIdx.x / gridDim.x);
-  const int c1 = (int)((int64_t)chunks * (blockIdx.x + 1) / gridDim.x);
-  if (c0 >= c1) return;
-  int ti = owner_of(pk, c0);
-  for (int ch = c0; ch < c1; ++ch) {
-    while (pk.start[ti + 1] <= ch) ++ti;
-    const int64_t e0 = (int64_t)(ch - pk.start[ti]) * CARE_EMA_CHUNK;
-    const int64_t left = pk.t[ti].n - e0;
-    const int len = left < CARE_EMA_CHUNK ? (int)left : CARE_EMA_CHUNK;
+  care_sweep_tensors(pk, chunks, [&](int ti, int64_t e0, int len) {
     float* t = pk.t[ti].t + e0;
     const float* s = pk.t[ti].s + e0;
-    if (((((uintptr_t)t) | ((uintptr_t)s)) & 15u) == 0) {
-      const int n4 = len >> 2, tail = len & 3;
-      if (tid < n4) {
-        float4 T = reinterpret_cast<float4*>(t)[tid];
-        const float4 S = reinterpret_cast<const float4*>(s)[tid];
-        T.x = ema_one(T.x, S.x, w, omw);
-        T.y = ema_one(T.y, S.y, w, omw);
-        T.z = ema_one(T.z, S.z, w, omw);
-        T.w = ema_one(T.w, S.w, w, omw);
-        reinterpret_cast<float4*>(t)[tid] = T;
-      }
-      if (tid < tail) {
-        const int i = 4 * n4 + tid;
-        t[i] = ema_one(t[i], s[i], w, omw);
-      }
-    } else {
-      for (int i = tid; i < len; i += IT) t[i] = ema_one(t[i], s[i], w, omw);
-    }
-  }
+    care_sweep_lanes(len, ((((uintptr_t)t) | ((uintptr_t)s)) & 15u) == 0, tid,
+                     [&](int i) {
+                       float4 T = reinterpret_cast<float4*>(t)[i];
+                       const float4 S = reinterpret_cast<const float4*>(s)[i];
+                       T.x = ema_one(T.x, S.x, w, omw);
+                       T.y = ema_one(T.y, S.y, w, omw);
+                       T.z = ema_one(T.z, S.z, w, omw);
+                       T.w = ema_one(T.w, S.w, w, omw);
+                       reinterpret_cast<float4*>(t)[i] = T;
+                     },
+                     [&](int i) { t[i] = ema_one(t[i], s[i], w, omw); });
+  });
 }
 
 // How one array of n floats at `base` is walked: `head` scalars up to the 16-byte boundary (all n when the arrays of a
 // call do not share a phase: `vec` = false), then the chunks of the n - head behind them.
 struct mse_walk {
-  int64_t head, chunks;
+  int64_t head;
   bool vec;
 };
 
@@ -94,8 +63,6 @@ __device__ __forceinline__ mse_walk mse_plan(uintptr_t a, uintptr_t others_xor, 
   } else {
     wk.head = 0;
   }
-  const int64_t body = n - wk.head;
-  wk.chunks = body / CARE_EMA_CHUNK + (body % CARE_EMA_CHUNK != 0);
   return wk;
 }
 
@@ -105,7 +72,7 @@ __device__ __forceinline__ void mse_acc(double& acc, float a, float b) {
 }
 
 // partials[w] = sum over workgroup w's chunks of (a - b)^2, in double from the lane upward (0 for a workgroup without
-// chunks; workgroup 0 takes the peeled head too)
+// chunks; workgroup 0 takes the peeled head too, before its chunks)
 __global__ __launch_bounds__(IT) void mse_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t n,
                                                          double* __restrict__ partials) {
   __shared__ double sm[IT / 64];
@@ -113,48 +80,29 @@ __global__ __launch_bounds__(IT) void mse_partial_kernel(const float* __restrict
   const mse_walk wk = mse_plan((uintptr_t)a, ((uintptr_t)a) ^ ((uintptr_t)b), n);
   double acc = 0.0;
   if (blockIdx.x == 0 && tid < wk.head) mse_acc(acc, a[tid], b[tid]);
-  const float* A = a + wk.head;
-  const float* B = b + wk.head;
-  const int64_t body = n - wk.head;
-  const int64_t c0 = wk.chunks * blockIdx.x / gridDim.x;
-  const int64_t c1 = wk.chunks * (blockIdx.x + 1) / gridDim.x;
-  for (int64_t ch = c0; ch < c1; ++ch) {
-    const int64_t e0 = ch * CARE_EMA_CHUNK;
-    const int64_t left = body - e0;
-    const int len = left < CARE_EMA_CHUNK ? (int)left : CARE_EMA_CHUNK;
-    if (wk.vec) {
-      const int n4 = len >> 2, tail = len & 3;
-      if (tid < n4) {
-        const float4 x = reinterpret_cast<const float4*>(A + e0)[tid];
-        const float4 y = reinterpret_cast<const float4*>(B + e0)[tid];
-        mse_acc(acc, x.x, y.x);
-        mse_acc(acc, x.y, y.y);
-        mse_acc(acc, x.z, y.z);
-        mse_acc(acc, x.w, y.w);
-      }
-      if (tid < tail) mse_acc(acc, A[e0 + 4 * n4 + tid], B[e0 + 4 * n4 + tid]);
-    } else {
-      for (int i = tid; i < len; i += IT) mse_acc(acc, A[e0 + i], B[e0 + i]);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if ((tid & 63) == 0) sm[tid >> 6] = acc;
-  __syncthreads();
-  if (tid == 0) partials[blockIdx.x] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  care_sweep_array(n - wk.head, [&](int64_t e0, int len) {
+    const float* A = a + wk.head + e0;
+    const float* B = b + wk.head + e0;
+    care_sweep_lanes(len, wk.vec, tid,
+                     [&](int i) {
+                       const float4 x = reinterpret_cast<const float4*>(A)[i];
+                       const float4 y = reinterpret_cast<const float4*>(B)[i];
+                       mse_acc(acc, x.x, y.x);
+                       mse_acc(acc, x.y, y.y);
+                       mse_acc(acc, x.z, y.z);
+                       mse_acc(acc, x.w, y.w);
+                     },
+                     [&](int i) { mse_acc(acc, A[i], B[i]); });
+  });
+  const double s = care_block_sum(acc, sm);
+  if (tid == 0) partials[blockIdx.x] = s;
 }
 
-// *loss = (float)((partials[0] + partials[1] + ...) / n): lane t adds t, t + 256, ..., the lanes meet in a fixed order
+// *loss = (float)((partials[0] + partials[1] + ...) / n)
 __global__ __launch_bounds__(IT) void mse_finish_kernel(const double* partials, int count, int64_t n, float* loss) {
   __shared__ double sm[IT / 64];
-  const int tid = threadIdx.x;
-  double d = 0.0;
-  for (int i = tid; i < count; i += IT) d += partials[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-  if ((tid & 63) == 0) sm[tid >> 6] = d;
-  __syncthreads();
-  if (tid == 0) *loss = (float)(((sm[0] + sm[1]) + (sm[2] + sm[3])) / (double)n);
+  const double s = care_partials_finish(partials, count, sm);
+  if (threadIdx.x == 0) *loss = (float)(s / (double)n);
 }
 
 __device__ __forceinline__ float mse_grad_one(float a, float b, float c) {
@@ -168,39 +116,23 @@ __global__ __launch_bounds__(IT) void mse_bwd_kernel(const float* a, const float
   const float c = (float)(2.0 * (double)*g / (double)n);
   const mse_walk wk = mse_plan((uintptr_t)a, (((uintptr_t)a) ^ ((uintptr_t)b)) | (((uintptr_t)a) ^ ((uintptr_t)da)), n);
   if (blockIdx.x == 0 && tid < wk.head) da[tid] = mse_grad_one(a[tid], b[tid], c);
-  const float* A = a + wk.head;
-  const float* B = b + wk.head;
-  float* D = da + wk.head;
-  const int64_t body = n - wk.head;
-  const int64_t c0 = wk.chunks * blockIdx.x / gridDim.x;
-  const int64_t c1 = wk.chunks * (blockIdx.x + 1) / gridDim.x;
-  for (int64_t ch = c0; ch < c1; ++ch) {
-    const int64_t e0 = ch * CARE_EMA_CHUNK;
-    const int64_t left = body - e0;
-    const int len = left < CARE_EMA_CHUNK ? (int)left : CARE_EMA_CHUNK;
-    if (wk.vec) {
-      const int n4 = len >> 2, tail = len & 3;
-      if (tid < n4) {
-        const float4 x = reinterpret_cast<const float4*>(A + e0)[tid];
-        const float4 y = reinterpret_cast<const float4*>(B + e0)[tid];
-        float4 r;
-        r.x = mse_grad_one(x.x, y.x, c);
-        r.y = mse_grad_one(x.y, y.y, c);
-        r.z = mse_grad_one(x.z, y.z, c);
-        r.w = mse_grad_one(x.w, y.w, c);
-        reinterpret_cast<float4*>(D + e0)[tid] = r;
-      }
-      if (tid < tail) { const int64_t i = e0 + 4 * n4 + tid; D[i] = mse_grad_one(A[i], B[i], c); }
-    } else {
-      for (int i = tid; i < len; i += IT) D[e0 + i] = mse_grad_one(A[e0 + i], B[e0 + i], c);
-    }
-  }
-}
-
-int mse_grid(int64_t n) {
-  if (n <= 0) return 1;
-  const int64_t c = n / CARE_EMA_CHUNK + (n % CARE_EMA_CHUNK != 0);
-  return (int)(c < IGRID ? c : IGRID);
+  care_sweep_array(n - wk.head, [&](int64_t e0, int len) {
+    const float* A = a + wk.head + e0;
+    const float* B = b + wk.head + e0;
+    float* D = da + wk.head + e0;
+    care_sweep_lanes(len, wk.vec, tid,
+                     [&](int i) {
+                       const float4 x = reinterpret_cast<const float4*>(A)[i];
+                       const float4 y = reinterpret_cast<const float4*>(B)[i];
+                       float4 r;
+                       r.x = mse_grad_one(x.x, y.x, c);
+                       r.y = mse_grad_one(x.y, y.y, c);
+                       r.z = mse_grad_one(x.z, y.z, c);
+                       r.w = mse_grad_one(x.w, y.w, c);
+                       reinterpret_cast<float4*>(D)[i] = r;
+                     },
+                     [&](int i) { D[i] = mse_grad_one(A[i], B[i], c); });
+  });
 }
 
 }  // namespace
@@ -210,20 +142,19 @@ extern "C" int care_ema_step(const care_ema_tensor* tensors, int count, double w
   if (bad) return bad;
   if (count == 0) return 0;
   const float wf = (float)w, omw = (float)one_minus_w;
-  return care_ema_for_each_pack(tensors, count, [&](const care_ema_pack& pk, int chunks, int) {
+  return care_sweep_for_each_pack<CARE_EMA_PACK>(tensors, count, [&](const care_ema_pack& pk, int chunks, int) {
     if (chunks == 0) return 0;
-    const int grid = chunks < IGRID ? chunks : IGRID;
-    hipLaunchKernelGGL(ema_step_kernel, dim3(grid), dim3(IT), 0, IST, pk, chunks, wf, omw);
+    hipLaunchKernelGGL(ema_step_kernel, dim3(care_sweep_grid(chunks)), dim3(IT), 0, IST, pk, chunks, wf, omw);
     return care_launch_status();
   });
 }
 
-extern "C" int care_mse_partials(int64_t n) { return mse_grid(n); }
+extern "C" int care_mse_partials(int64_t n) { return care_sweep_grid(care_sweep_chunks(n)); }
 
 extern "C" int care_mse_fwd(const float* a, const float* b, int64_t n, double* partials, float* loss, void* stream) {
   if (!a || !b || !partials || !loss || n <= 0) return CARE_EINVAL;
   if (((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)loss)) & 3u) || (((uintptr_t)partials) & 7u)) return CARE_EALIGN;
-  const int grid = mse_grid(n);
+  const int grid = care_mse_partials(n);
   hipLaunchKernelGGL(mse_partial_kernel, dim3(grid), dim3(IT), 0, IST, a, b, n, partials);
   int rc = care_launch_status();
   if (rc) return rc;
@@ -234,6 +165,6 @@ extern "C" int care_mse_fwd(const float* a, const float* b, int64_t n, double* p
 extern "C" int care_mse_bwd(const float* a, const float* b, int64_t n, const float* g, float* da, void* stream) {
   if (!a || !b || !g || !da || n <= 0) return CARE_EINVAL;
   if ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)g) | ((uintptr_t)da)) & 3u) return CARE_EALIGN;
-  hipLaunchKernelGGL(mse_bwd_kernel, dim3(mse_grid(n)), dim3(IT), 0, IST, a, b, n, g, da);
+  hipLaunchKernelGGL(mse_bwd_kernel, dim3(care_mse_partials(n)), dim3(IT), 0, IST, a, b, n, g, da);
   return care_launch_status();
 }

@@ -4,89 +4,41 @@
 //
 // 32 B per element and step (norm: read g; update: read p, g, m, v, write p, m, v) and ~40 VALU operations: a streaming
 // kernel.  The tensor list (55 tensors from 500 to 5.4 M elements in msrvtt_care) reaches the kernel BY VALUE in its
-// arguments (optim_pack.h: 64 descriptors a launch) - gradients are fresh allocations every step, so a device-side table
-// would be an upload per step.  Every tensor is cut into chunks of 1024 elements (a small tensor is one short chunk), a
-// grid of at most 2048 workgroups of 256 splits the launch's chunks into contiguous ranges of equal length (+-1), and a
-// workgroup walks its range with the tensor index moving along.  A chunk whose four pointers are 16-byte aligned moves as
-// one float4 per lane and array (+ 0..3 tail scalars in a tensor's last chunk); any other chunk as scalars.
-//
-// No floating-point atomics: a workgroup's sum of squares goes to a partial of its own (double), a second one-workgroup
-// kernel adds the partials in index order.
+// arguments (sweep.h: CARE_OPT_PACK descriptors a launch) - gradients are fresh allocations every step, so a device-side
+// table would be an upload per step.  The cut into chunks, the walk, the lanes of a chunk and the sums are sweep.h's.
 #include "care_common.h"
-#include "optim_pack.h"
+#include "sweep.h"
 
 namespace {
 
 #define OST ((hipStream_t)stream)
-constexpr int OT = 256;
-static_assert(CARE_OPT_CHUNK == 4 * OT, "a chunk is one float4 per lane");
+constexpr int OT = CARE_SWEEP_THREADS;
 static_assert(sizeof(care_opt_tensor) == 48 && sizeof(care_opt_pack) <= 3584, "the pack and the scalars fit the 4-KB argument block");
-
-// the tensor that owns chunk ch of the pack: the last i with start[i] <= ch (an empty tensor never is)
-__device__ __forceinline__ int owner_of(const care_opt_pack& pk, int ch) {
-  int lo = 0, hi = pk.count;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (pk.start[mid] <= ch) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
-__device__ __forceinline__ void chunk_range(int chunks, int& c0, int& c1) {
-  c0 = (int)((int64_t)chunks * blockIdx.x / gridDim.x);
-  c1 = (int)((int64_t)chunks * (blockIdx.x + 1) / gridDim.x);
-}
 
 // partials[b] (+)= sum of g^2 over workgroup b's chunks.  first != 0: the launch that opens a list writes every
 // partial (0 for a workgroup without chunks); the launches behind it add in stream order.
 __global__ __launch_bounds__(OT) void grad_sqnorm_kernel(const care_opt_pack pk, int chunks, double* partials, int first) {
   __shared__ double sm[OT / 64];
   const int tid = threadIdx.x;
-  int c0, c1;
-  chunk_range(chunks, c0, c1);
-  float acc = 0.f;
-  if (c0 < c1) {
-    int ti = owner_of(pk, c0);
-    for (int ch = c0; ch < c1; ++ch) {
-      while (pk.start[ti + 1] <= ch) ++ti;
-      const int64_t e0 = (int64_t)(ch - pk.start[ti]) * CARE_OPT_CHUNK;
-      const int64_t left = pk.t[ti].n - e0;
-      const int len = left < CARE_OPT_CHUNK ? (int)left : CARE_OPT_CHUNK;
-      const float* g = pk.t[ti].g + e0;
-      if ((((uintptr_t)g) & 15u) == 0) {
-        const int n4 = len >> 2, tail = len & 3;
-        if (tid < n4) {
-          const float4 q = reinterpret_cast<const float4*>(g)[tid];
-          acc += (q.x * q.x + q.y * q.y) + (q.z * q.z + q.w * q.w);
-        }
-        if (tid < tail) { const float x = g[4 * n4 + tid]; acc += x * x; }
-      } else {
-        for (int i = tid; i < len; i += OT) { const float x = g[i]; acc += x * x; }
-      }
-    }
-  }
-  double d = (double)acc;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-  if ((tid & 63) == 0) sm[tid >> 6] = d;
-  __syncthreads();
-  if (tid == 0) {
-    const double s = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    partials[blockIdx.x] = first ? s : partials[blockIdx.x] + s;
-  }
+  float acc = 0.f;  // in float across the chunks; double from the shuffle upward
+  care_sweep_tensors(pk, chunks, [&](int ti, int64_t e0, int len) {
+    const float* g = pk.t[ti].g + e0;
+    care_sweep_lanes(len, (((uintptr_t)g) & 15u) == 0, tid,
+                     [&](int i) {
+                       const float4 q = reinterpret_cast<const float4*>(g)[i];
+                       acc += (q.x * q.x + q.y * q.y) + (q.z * q.z + q.w * q.w);
+                     },
+                     [&](int i) { const float x = g[i]; acc += x * x; });
+  });
+  const double s = care_block_sum((double)acc, sm);
+  if (tid == 0) partials[blockIdx.x] = first ? s : partials[blockIdx.x] + s;
 }
 
-// *norm = sqrt(partials[0] + partials[1] + ...): lane t adds t, t + 256, ..., the lanes meet in a fixed order
+// *norm = sqrt(partials[0] + partials[1] + ...)
 __global__ __launch_bounds__(OT) void grad_norm_finish_kernel(const double* partials, int n, float* norm) {
   __shared__ double sm[OT / 64];
-  const int tid = threadIdx.x;
-  double d = 0.0;
-  for (int i = tid; i < n; i += OT) d += partials[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
-  if ((tid & 63) == 0) sm[tid >> 6] = d;
-  __syncthreads();
-  if (tid == 0) *norm = (float)sqrt((sm[0] + sm[1]) + (sm[2] + sm[3]));
+  const double s = care_partials_finish(partials, n, sm);
+  if (threadIdx.x == 0) *norm = (float)sqrt(s);
 }
 
 struct adam_consts {
@@ -108,8 +60,8 @@ __global__ __launch_bounds__(OT) void adam_step_kernel(const care_opt_pack pk, i
                                                        float eps, float bias2_sqrt, const float* norm, float max_norm) {
   const int tid = threadIdx.x;
   int c0, c1;
-  chunk_range(chunks, c0, c1);
-  if (c0 >= c1) return;
+  care_sweep_range(chunks, c0, c1);
+  if (c0 >= c1) return;  // ahead of the read of *norm, so that all arguments load in one batch before it
   adam_consts k;
   k.clip = 1.f;
   if (norm) {  // clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1 (a NaN stays a NaN)
@@ -117,52 +69,38 @@ __global__ __launch_bounds__(OT) void adam_step_kernel(const care_opt_pack pk, i
     k.clip = q > 1.f ? 1.f : q;
   }
   k.omb1 = omb1; k.beta2 = beta2; k.omb2 = omb2; k.bias2_sqrt = bias2_sqrt; k.eps = eps;
-  int ti = owner_of(pk, c0);
-  for (int ch = c0; ch < c1; ++ch) {
-    while (pk.start[ti + 1] <= ch) ++ti;
-    const int64_t e0 = (int64_t)(ch - pk.start[ti]) * CARE_OPT_CHUNK;
-    const int64_t left = pk.t[ti].n - e0;
-    const int len = left < CARE_OPT_CHUNK ? (int)left : CARE_OPT_CHUNK;
+  care_sweep_tensors(pk, chunks, [&](int ti, int64_t e0, int len) {
     float* p = pk.t[ti].p + e0;
     const float* g = pk.t[ti].g + e0;
     float* m = pk.t[ti].m + e0;
     float* v = pk.t[ti].v + e0;
     k.wd = pk.t[ti].weight_decay;
     k.neg_step = -pk.t[ti].step_size;
-    if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0) {
-      const int n4 = len >> 2, tail = len & 3;
-      if (tid < n4) {
-        float4 P = reinterpret_cast<float4*>(p)[tid];
-        const float4 G = reinterpret_cast<const float4*>(g)[tid];
-        float4 M = reinterpret_cast<float4*>(m)[tid];
-        float4 V = reinterpret_cast<float4*>(v)[tid];
-        adam_one(P.x, G.x, M.x, V.x, k);
-        adam_one(P.y, G.y, M.y, V.y, k);
-        adam_one(P.z, G.z, M.z, V.z, k);
-        adam_one(P.w, G.w, M.w, V.w, k);
-        reinterpret_cast<float4*>(p)[tid] = P;
-        reinterpret_cast<float4*>(m)[tid] = M;
-        reinterpret_cast<float4*>(v)[tid] = V;
-      }
-      if (tid < tail) {
-        const int i = 4 * n4 + tid;
-        float P = p[i], M = m[i], V = v[i];
-        adam_one(P, g[i], M, V, k);
-        p[i] = P; m[i] = M; v[i] = V;
-      }
-    } else {
-      for (int i = tid; i < len; i += OT) {
-        float P = p[i], M = m[i], V = v[i];
-        adam_one(P, g[i], M, V, k);
-        p[i] = P; m[i] = M; v[i] = V;
-      }
-    }
-  }
+    care_sweep_lanes(len, ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15u) == 0, tid,
+                     [&](int i) {
+                       float4 P = reinterpret_cast<float4*>(p)[i];
+                       const float4 G = reinterpret_cast<const float4*>(g)[i];
+                       float4 M = reinterpret_cast<float4*>(m)[i];
+                       float4 V = reinterpret_cast<float4*>(v)[i];
+                       adam_one(P.x, G.x, M.x, V.x, k);
+                       adam_one(P.y, G.y, M.y, V.y, k);
+                       adam_one(P.z, G.z, M.z, V.z, k);
+                       adam_one(P.w, G.w, M.w, V.w, k);
+                       reinterpret_cast<float4*>(p)[i] = P;
+                       reinterpret_cast<float4*>(m)[i] = M;
+                       reinterpret_cast<float4*>(v)[i] = V;
+                     },
+                     [&](int i) {
+                       float P = p[i], M = m[i], V = v[i];
+                       adam_one(P, g[i], M, V, k);
+                       p[i] = P; m[i] = M; v[i] = V;
+                     });
+  });
 }
 
 }  // namespace
 
-extern "C" int care_grad_sqnorm_partials(int64_t total) { return care_opt_partials(total); }
+extern "C" int care_grad_sqnorm_partials(int64_t total) { return care_sweep_grid(care_sweep_chunks(total)); }
 
 extern "C" int care_grad_sqnorm(const care_opt_tensor* tensors, int count, double* partials, float* norm, void* stream) {
   if (!partials || !norm) return CARE_EINVAL;
@@ -170,12 +108,12 @@ extern "C" int care_grad_sqnorm(const care_opt_tensor* tensors, int count, doubl
   int64_t total = 0;
   const int bad = care_opt_check(tensors, count, &total);
   if (bad) return bad;
-  const int grid = care_opt_partials(total);
+  const int grid = care_grad_sqnorm_partials(total);
   if (count == 0) {  // one empty launch: every partial (there is one) = 0
     care_opt_pack pk = {};
     hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(grid), dim3(OT), 0, OST, pk, 0, partials, 1);
   }
-  const int rc = care_opt_for_each_pack(tensors, count, [&](const care_opt_pack& pk, int chunks, int li) {
+  const int rc = care_sweep_for_each_pack<CARE_OPT_PACK>(tensors, count, [&](const care_opt_pack& pk, int chunks, int li) {
     hipLaunchKernelGGL(grad_sqnorm_kernel, dim3(grid), dim3(OT), 0, OST, pk, chunks, partials, li == 0 ? 1 : 0);
     return care_launch_status();
   });
@@ -192,11 +130,10 @@ extern "C" int care_adam_step(const care_opt_tensor* tensors, int count, double 
   if (count == 0) return 0;
   if (!(bias2_sqrt > 0.0)) return CARE_EINVAL;
   const float omb1 = (float)(1.0 - beta1), b2 = (float)beta2, omb2 = (float)(1.0 - beta2);
-  return care_opt_for_each_pack(tensors, count, [&](const care_opt_pack& pk, int chunks, int) {
+  return care_sweep_for_each_pack<CARE_OPT_PACK>(tensors, count, [&](const care_opt_pack& pk, int chunks, int) {
     if (chunks == 0) return 0;
-    const int grid = chunks < 2048 ? chunks : 2048;
-    hipLaunchKernelGGL(adam_step_kernel, dim3(grid), dim3(OT), 0, OST, pk, chunks, omb1, b2, omb2, (float)eps, (float)bias2_sqrt,
-                       norm, (float)max_norm);
+    hipLaunchKernelGGL(adam_step_kernel, dim3(care_sweep_grid(chunks)), dim3(OT), 0, OST, pk, chunks, omb1, b2, omb2, (float)eps,
+                       (float)bias2_sqrt, norm, (float)max_norm);
     return care_launch_status();
   });
 }

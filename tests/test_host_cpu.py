@@ -150,15 +150,9 @@ def test_abi_library_exports_every_declared_symbol():
     assert loaded.care_h16() == b"bf16" and _lib.load(variant="f16").care_h16() == b"fp16"
     assert _lib.load(variant="f16").care_build_flags() == b"-DCARE_H16_FP16" and loaded.care_build_flags() == b""
     # the two structs of care_decode_resident: ctypes mirrors against the C compiler's layout of the header
-    import subprocess
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sz.c")
-        open(src, "w").write('#include <stdio.h>\n#include <stddef.h>\n#include "care_hip.h"\nint main(void) { printf("%zu %zu %zu %zu\\n", '
-                             'sizeof(care_resident_attn), sizeof(care_resident_layer), offsetof(care_resident_layer, n_att), '
-                             'offsetof(care_resident_attn, bias)); return 0; }\n')
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", os.path.join(td, "sz")], check=True)
-        sizes = [int(v) for v in subprocess.run([os.path.join(td, "sz")], capture_output=True, text=True, check=True).stdout.split()]
+    from c_layout import c_layout
+    sizes = c_layout(["sizeof(care_resident_attn)", "sizeof(care_resident_layer)", "offsetof(care_resident_layer, n_att)",
+                      "offsetof(care_resident_attn, bias)"])
     assert sizes == [ctypes.sizeof(_lib.ResidentAttn), ctypes.sizeof(_lib.ResidentLayer), _lib.ResidentLayer.n_att.offset,
                      _lib.ResidentAttn.bias.offset]
     assert loaded.care_decode_resident_scratch(1, 512, 2048, 10547) == 53248 + 16 * (512 * 18 + 2048 * 2 + 165 * 12)

@@ -4,13 +4,12 @@ launch), and `InterplayStep`'s bookkeeping on CPU modules (models/Wrapper.py:550
 import ctypes
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 import torch
 
 import interplay_reference as R
+from c_layout import c_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRY_POINTS = ("care_ema_step", "care_mse_fwd", "care_mse_bwd")
@@ -50,13 +49,8 @@ def test_header_binding_and_libraries_agree_on_the_mean_teacher_entry_points():
 def test_the_descriptor_mirrors_the_c_layout():
     from care_amd import _lib
 
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sz.c")
-        open(src, "w").write('#include <stdio.h>\n#include <stddef.h>\n#include "care_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %d\\n", '
-                             'sizeof(care_ema_tensor), offsetof(care_ema_tensor, t), offsetof(care_ema_tensor, s), '
-                             'offsetof(care_ema_tensor, n), CARE_EMA_PACK); return 0; }\n')
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", os.path.join(td, "sz")], check=True)
-        sizes = [int(v) for v in subprocess.run([os.path.join(td, "sz")], capture_output=True, text=True, check=True).stdout.split()]
+    sizes = c_layout(["sizeof(care_ema_tensor)", "offsetof(care_ema_tensor, t)", "offsetof(care_ema_tensor, s)",
+                      "offsetof(care_ema_tensor, n)", "CARE_EMA_PACK"])
     T = _lib.EmaTensor
     assert sizes[:4] == [ctypes.sizeof(T), T.t.offset, T.s.offset, T.n.offset]
     # the pack (descriptors, a first chunk each and one more, the count) and the kernel's three scalars fit the 4-KB argument block

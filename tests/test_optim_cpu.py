@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import optim_reference as R
+from c_layout import c_layout
 from care_amd import optim as care_optim
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -241,15 +242,8 @@ def test_header_binding_and_libraries_agree_on_the_optimiser_entry_points():
     for cite in ("models/Wrapper.py:316-386", "train.py:128", "misc/utils.py:282-304"):
         assert cite in block
     # the descriptor: ctypes mirror against the C compiler's layout of the header
-    import subprocess
-    import tempfile
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "sz.c")
-        open(src, "w").write('#include <stdio.h>\n#include <stddef.h>\n#include "care_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %d\\n", '
-                             'sizeof(care_opt_tensor), offsetof(care_opt_tensor, n), offsetof(care_opt_tensor, step_size), '
-                             'offsetof(care_opt_tensor, weight_decay), CARE_OPT_PACK); return 0; }\n')
-        subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", os.path.join(td, "sz")], check=True)
-        sizes = [int(v) for v in subprocess.run([os.path.join(td, "sz")], capture_output=True, text=True, check=True).stdout.split()]
+    sizes = c_layout(["sizeof(care_opt_tensor)", "offsetof(care_opt_tensor, n)", "offsetof(care_opt_tensor, step_size)",
+                      "offsetof(care_opt_tensor, weight_decay)", "CARE_OPT_PACK"])
     T = _lib.OptTensor
     assert sizes == [ctypes.sizeof(T), T.n.offset, T.step_size.offset, T.weight_decay.offset, 64]
     # the host-side checks need no device: they return before anything is launched
