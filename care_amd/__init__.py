@@ -10,6 +10,8 @@ and the mean-teacher step of `--wrapper InterplayModel` (models/Wrapper.py:550-6
     from care_amd import InterplayStep, distillation_mse, ema_update
 and the `r` modality retrieved on device from a bank of caption embeddings (pretreatment/clip_retrieval.py; care_amd/retrieval.py):
     from care_amd import CaptionBank, attach_retrieval
+and self-critical sequence training on the CIDEr-D of sampled captions (care_amd/reward.py, care_amd/scst.py):
+    from care_amd import CiderBank, self_critical_loss, SelfCriticalStep
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
@@ -17,7 +19,9 @@ from .criterion import Criterion, LanguageGeneration, NoisyOrMIL, get_criterion 
 from .optim import Adam, configure_optimizers, filter_weight_decay  # noqa: F401
 from .interplay import InterplayStep, distillation_mse, ema_update  # noqa: F401
 from .retrieval import CaptionBank, attach_retrieval  # noqa: F401
+from .reward import CiderBank, self_critical_loss  # noqa: F401
+from .scst import SelfCriticalStep  # noqa: F401
 
-__all__ = ["get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+__all__ = ["CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
            "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
            "CaptionBank", "attach_retrieval"]

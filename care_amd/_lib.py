@@ -121,6 +121,10 @@ SIGNATURES = {
     "care_retrieval_query": [_P, _P, _I, _I, _I, _P],
     "care_retrieval_topk": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "care_retrieval_gather": [_P, _I, _I, _P, _I, _P, _P],
+    "care_cider_score": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "care_reward_advantage": [_P, _P, _I, _I, _P, _P, _P],
+    "care_reward_loss_fwd": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "care_reward_loss_bwd": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
 }
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
@@ -162,6 +166,13 @@ class OptTensor(ctypes.Structure):
 class EmaTensor(ctypes.Structure):
     """care_ema_tensor (include/care_hip.h)."""
     _fields_ = [("t", c_void_p), ("s", c_void_p), ("n", c_int64)]
+
+
+class CiderBankDesc(ctypes.Structure):
+    """care_cider_bank (include/care_hip.h)."""
+    _fields_ = [("corpus_keys", c_void_p), ("corpus_lndf", c_void_p), ("n_corpus", c_int64), ("ref_keys", c_void_p),
+                ("ref_w", c_void_p), ("ref_start", c_void_p), ("ref_norm", c_void_p), ("ref_len", c_void_p),
+                ("vid_start", c_void_p), ("n_videos", ctypes.c_int32), ("n_refs", ctypes.c_int32), ("ln_n", ctypes.c_double)]
 
 
 _libs = {}

@@ -1,0 +1,289 @@
+"""The reward and the loss of self-critical sequence training on the MI355X (csrc/reward.hip).
+
+    from care_amd.reward import CiderBank, reward_advantage, self_critical_loss
+
+`CiderBank` holds the reference captions of a corpus in the form care_cider_score reads: the coco-caption CIDEr-D over integer
+token ids (restated in float64 in tests/cider_reference.py).  Building the bank is setup - numpy on the host, once: every
+n-gram (n = 1..4) packed into one uint64, 16 bits a token with the orders below 4 zero-filled (PAD = 0 never occurs inside a
+caption, so the order is implied and nothing collides), `np.unique` for the per-video sets and the document frequencies.
+`bank.score` is one launch, a workgroup per candidate, and reads the `fed` / `length` device tensors of
+HipEngine.translate_sample / translate_greedy as they are; `reward_advantage` forms advantages against the greedy caption's
+reward or the leave-one-out mean of a clip's other samples; `self_critical_loss` is the advantage-weighted log-likelihood
+
+    loss = -(1 / n_live) * sum over live (r, j) of adv[r] * logp[r, j],   logp[r, j] = x[y] - logsumexp(x)
+
+with its backward to the logits.  n_live, the upstream gradient and every reward stay on the device: nothing here waits for it.
+
+As everywhere in care_amd there is no CPU fallback: CPU tensors raise.  A `DeferredLogits` (model.set_fused_head(True)) is
+refused by name - the loss is taken over the [N, t, V] logits the fused head never materialises.
+"""
+import ctypes
+import math
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from .constants import EOS, PAD
+from .criterion import DeferredLogits
+
+__all__ = ["CiderBank", "reward_advantage", "self_critical_loss", "pack_ngrams", "MAX_CAPTION"]
+
+MAX_CAPTION = 64      # tokens of a candidate caption (csrc/reward.hip: 250 n-grams in LDS)
+MAX_VOCAB = 1 << 16   # 16 bits a token in an n-gram's key
+ORDERS = 4
+
+
+def pack_ngrams(tokens: Sequence[int], n: int) -> np.ndarray:
+    """The n-grams of `tokens`, in caption order, as uint64 keys: token j of an n-gram in bits [16 j, 16 j + 16)."""
+    toks = np.asarray(tokens, dtype=np.uint64).reshape(-1)
+    m = toks.size - n + 1
+    if m <= 0:
+        return np.zeros(0, dtype=np.uint64)
+    keys = np.zeros(m, dtype=np.uint64)
+    for j in range(n):
+        keys |= toks[j: j + m] << np.uint64(16 * j)
+    return keys
+
+
+def key_order(keys: np.ndarray) -> np.ndarray:
+    """The order (1..4) of packed keys: the highest non-zero 16-bit group (no token inside a caption is 0)."""
+    keys = np.asarray(keys, dtype=np.uint64)
+    return ((keys >> np.uint64(16)) != 0).astype(np.int64) + ((keys >> np.uint64(32)) != 0) + ((keys >> np.uint64(48)) != 0) + 1
+
+
+def _need_device(t, what: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("`{}` must be a tensor, got {}".format(what, type(t).__name__))
+    if t.device.type != "cuda":
+        raise RuntimeError("`{}` is on `{}`: the reward and its loss run on the MI355X (no CPU fallback)".format(what, t.device))
+
+
+class CiderBank(object):
+    """The reference captions of a corpus, on the device.  refs: one entry per video, each a list of token-id lists (a trailing
+    EOS is dropped unless with_eos; then it stays an ordinary token, in the references and in the candidates).  video_ids
+    (optional): the name of each entry as the loader's batch["video_ids"] gives it; default: entry i is video i."""
+
+    def __init__(self, refs: Sequence[Sequence[Sequence[int]]], vocab_size: int, with_eos: bool = False, device="cuda",
+                 video_ids: Optional[Sequence] = None):
+        if not isinstance(vocab_size, int) or vocab_size < 1:
+            raise ValueError("`vocab_size` must be a positive integer, got {!r}".format(vocab_size))
+        if vocab_size > MAX_VOCAB:
+            raise ValueError("`vocab_size` {} > {}: an n-gram's key holds 16 bits a token".format(vocab_size, MAX_VOCAB))
+        refs = list(refs)
+        if not refs:
+            raise ValueError("`refs` is empty: CIDEr-D needs a corpus of at least one video")
+        if video_ids is not None and len(video_ids) != len(refs):
+            raise ValueError("{} `video_ids` for {} videos".format(len(video_ids), len(refs)))
+        self.vocab_size, self.with_eos, self.n_videos = vocab_size, bool(with_eos), len(refs)
+        self.device = None if device is None else torch.device(device)   # (None: the host tables only - `host` - nothing to score with)
+        if self.device is not None and self.device.type != "cuda":
+            raise RuntimeError("`device` is `{}`: the bank lives on the MI355X (no CPU fallback)".format(self.device))
+        self._row_of = None if video_ids is None else {v: i for i, v in enumerate(video_ids)}
+        if self._row_of is not None and len(self._row_of) != len(refs):
+            raise ValueError("`video_ids` holds a name twice")
+
+        # per reference: its caption, the sorted unique keys of all four orders and their counts
+        ref_keys, ref_tf, ref_len, vid_start, video_sets = [], [], [], [0], []
+        for v, video in enumerate(refs):
+            of_video = []
+            for ref in video:
+                toks = np.asarray(list(ref), dtype=np.int64).reshape(-1)
+                if toks.size and not self.with_eos and toks[-1] == EOS:
+                    toks = toks[:-1]
+                if toks.size and (toks.min() <= PAD or toks.max() >= vocab_size):
+                    raise ValueError("video {}: a reference holds a token outside [1, vocab_size = {})".format(v, vocab_size))
+                keys = np.concatenate([pack_ngrams(toks, n) for n in range(1, ORDERS + 1)])
+                uniq, counts = np.unique(keys, return_counts=True)
+                ref_keys.append(uniq)
+                ref_tf.append(counts.astype(np.float64))
+                ref_len.append(toks.size)
+                of_video.append(uniq)
+            vid_start.append(len(ref_keys))
+            video_sets.append(np.unique(np.concatenate(of_video)) if of_video else np.zeros(0, dtype=np.uint64))
+        corpus_keys, df = np.unique(np.concatenate(video_sets), return_counts=True)   # once per video
+        corpus_lndf = np.log(np.maximum(1, df).astype(np.float64))
+        self.ln_n = math.log(self.n_videos)
+
+        ref_start = np.zeros(len(ref_keys) + 1, dtype=np.int64)
+        np.cumsum(np.asarray([k.size for k in ref_keys], dtype=np.int64), out=ref_start[1:])
+        all_keys = np.concatenate(ref_keys) if ref_keys else np.zeros(0, dtype=np.uint64)
+        all_tf = np.concatenate(ref_tf) if ref_tf else np.zeros(0, dtype=np.float64)
+        all_w = all_tf * (self.ln_n - corpus_lndf[np.searchsorted(corpus_keys, all_keys)])
+        order = key_order(all_keys)
+        ref_norm = np.zeros((len(ref_keys), ORDERS), dtype=np.float64)
+        owner = np.repeat(np.arange(len(ref_keys)), np.diff(ref_start))
+        np.add.at(ref_norm, (owner, order - 1), all_w * all_w)
+        ref_norm = np.sqrt(ref_norm)
+
+        self.host = {"corpus_keys": corpus_keys, "corpus_lndf": corpus_lndf, "df": df, "ref_keys": all_keys, "ref_w": all_w,
+                     "ref_start": ref_start, "ref_norm": ref_norm, "ref_len": np.asarray(ref_len, dtype=np.int32),
+                     "vid_start": np.asarray(vid_start, dtype=np.int32)}
+        self.n_refs = len(ref_keys)
+
+        def up(a, dtype):   # (at least one element, so that no array of the bank is a NULL pointer)
+            a = np.ascontiguousarray(a)
+            if a.dtype == np.uint64:
+                a = a.view(np.int64)
+            if a.size == 0:
+                a = np.zeros(1, dtype=a.dtype)
+            return torch.from_numpy(a.copy()).to(dtype).to(self.device)
+
+        h = self.host
+        self.dev = self.desc = None
+        if self.device is None:
+            return
+        self.dev = {"corpus_keys": up(h["corpus_keys"], torch.int64), "corpus_lndf": up(h["corpus_lndf"], torch.float64),
+                    "ref_keys": up(h["ref_keys"], torch.int64), "ref_w": up(h["ref_w"], torch.float64),
+                    "ref_start": up(h["ref_start"], torch.int64), "ref_norm": up(h["ref_norm"].reshape(-1), torch.float64),
+                    "ref_len": up(h["ref_len"], torch.int32), "vid_start": up(h["vid_start"], torch.int32)}
+        self.desc = self._desc()
+
+    def _desc(self) -> "_lib.CiderBankDesc":
+        d, desc = self.dev, _lib.CiderBankDesc()
+        for k in ("corpus_keys", "corpus_lndf", "ref_keys", "ref_w", "ref_start", "ref_norm", "ref_len", "vid_start"):
+            setattr(desc, k, d[k].data_ptr())
+        desc.n_corpus, desc.n_videos, desc.n_refs, desc.ln_n = int(self.host["corpus_keys"].size), self.n_videos, self.n_refs, self.ln_n
+        return desc
+
+    def rows(self, video_ids) -> torch.Tensor:
+        """The bank rows (int32, on the bank's device) of a batch's `video_ids`: names through the `video_ids` the bank was
+        built with, integers (a list or a tensor, which is not read on the host) as they are."""
+        if isinstance(video_ids, torch.Tensor):
+            if self._row_of is not None:
+                raise TypeError("the bank was built with named `video_ids`: pass the batch's names, not a tensor")
+            return video_ids.to(self.device, torch.int32).reshape(-1)
+        ids = list(video_ids)
+        if self._row_of is not None:
+            missing = [v for v in ids if v not in self._row_of]
+            if missing:
+                raise KeyError("video_ids not in the bank: {}".format(missing[:4]))
+            ids = [self._row_of[v] for v in ids]
+        rows = torch.tensor([int(v) for v in ids], dtype=torch.int32)
+        return rows if self.device is None else rows.to(self.device)
+
+    def score(self, tokens: torch.Tensor, length: torch.Tensor, video: torch.Tensor, out: Optional[torch.Tensor] = None,
+              offset: int = 0, bad: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """fp32 [rows]: the CIDEr-D of caption r = tokens[r, offset : offset + length[r]] against the references of bank row
+        video[r].  tokens: int32 [rows, width] with unit stride in the last dimension and any row stride - a view such as
+        fed[:, 1:] is scored in place.  bad (optional, int32 [1]): the number of rows whose video is outside the bank."""
+        if self.desc is None:
+            raise RuntimeError("this bank was built with device=None (host tables only): CIDEr-D is scored on the MI355X")
+        for what, t in (("tokens", tokens), ("length", length), ("video", video)):
+            _need_device(t, what)
+            if t.dtype != torch.int32:
+                raise TypeError("`{}` must be int32, got {}".format(what, t.dtype))
+        if tokens.dim() != 2 or tokens.stride(1) != 1:
+            raise ValueError("`tokens` must be [rows, width] with unit stride in the last dimension, got shape {} strides {}".format(
+                tuple(tokens.shape), tuple(tokens.stride())))
+        rows, width = tokens.shape[0], tokens.shape[1] - int(offset)
+        if offset < 0 or width < 1:
+            raise ValueError("`offset` {} leaves no column of `tokens` {}".format(offset, tuple(tokens.shape)))
+        if width > MAX_CAPTION:
+            raise ValueError("captions of up to {} tokens: care_cider_score holds {}".format(width, MAX_CAPTION))
+        if length.numel() != rows or video.numel() != rows:
+            raise ValueError("`length` {} and `video` {} must hold one entry per row of `tokens` {}".format(
+                tuple(length.shape), tuple(video.shape), tuple(tokens.shape)))
+        length, video = length.contiguous(), video.contiguous()
+        ld = tokens.stride(0) if rows > 1 else max(tokens.stride(0), tokens.shape[1])
+        if out is None:
+            out = torch.empty(rows, dtype=torch.float32, device=tokens.device)
+        elif out.dtype != torch.float32 or out.numel() != rows or not out.is_contiguous() or out.device != tokens.device:
+            raise ValueError("`out` must be a contiguous fp32 tensor of {} entries on {}".format(rows, tokens.device))
+        with torch.cuda.device(tokens.device):
+            _lib.call("care_cider_score", _lib.ptr(tokens), ld, int(offset), width, _lib.ptr(length), _lib.ptr(video), rows,
+                      int(self.with_eos), EOS, ctypes.addressof(self.desc), _lib.ptr(out), _lib.ptr(bad), tag="cider_score")
+        return out
+
+
+def reward_advantage(reward: torch.Tensor, baseline: Optional[torch.Tensor] = None):
+    """(adv fp32 [B, n], stats float64 [2]) of reward [B, n]: adv = reward - baseline[b] with `baseline` [B] (the greedy
+    caption's reward), else reward minus the mean of the clip's OTHER n - 1 samples; stats = the mean reward and the mean
+    baseline, device doubles."""
+    _need_device(reward, "reward")
+    if reward.dim() != 2 or reward.dtype != torch.float32:
+        raise ValueError("`reward` must be fp32 [clips, samples], got {} {}".format(reward.dtype, tuple(reward.shape)))
+    B, n = reward.shape
+    if baseline is None and n < 2:
+        raise ValueError("the leave-one-out baseline needs n_samples >= 2, got {}".format(n))
+    if baseline is not None:
+        _need_device(baseline, "baseline")
+        if baseline.dtype != torch.float32 or baseline.numel() != B:
+            raise ValueError("`baseline` must be fp32 [{}], got {} {}".format(B, baseline.dtype, tuple(baseline.shape)))
+        baseline = baseline.contiguous()
+    reward = reward.contiguous()
+    adv = torch.empty_like(reward)
+    stats = torch.empty(2, dtype=torch.float64, device=reward.device)
+    with torch.cuda.device(reward.device):
+        _lib.call("care_reward_advantage", _lib.ptr(reward), _lib.ptr(baseline), B, n, _lib.ptr(adv), _lib.ptr(stats), tag="reward_adv")
+    return adv, stats
+
+
+class _WeightedLogLik(torch.autograd.Function):
+    """-(1 / n_live) sum adv[r] logp[r, j] over the live label positions; the gradient goes to the logits only."""
+
+    @staticmethod
+    def forward(ctx, logits, labels32, adv, acc):
+        N, tl, V = logits.shape
+        t = labels32.shape[1]
+        # whole sequences at one stride, rows at another: [N, t + 1, V] is walked in place, its last position skipped
+        if logits.stride(2) != 1 or logits.stride(1) < V or logits.stride(0) < t * logits.stride(1):
+            logits = logits.contiguous()
+        rows, dev = N * t, logits.device
+        stats = torch.empty(3, rows, device=dev, dtype=torch.float32)   # max, log sum exp(x - max), logp
+        totals = torch.empty(2, device=dev, dtype=torch.float64)        # sum adv logp, n_live
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        seq_logp = torch.empty(N, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.call("care_reward_loss_fwd", _lib.ptr(logits), logits.stride(1), logits.stride(0), t, V, _lib.ptr(labels32),
+                      _lib.ptr(adv), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]), _lib.ptr(totals), _lib.ptr(loss),
+                      _lib.ptr(seq_logp), _lib.ptr(acc), rows, tag="reward_loss_fwd")
+        ctx.save_for_backward(logits, labels32, adv, stats, totals)
+        ctx.mark_non_differentiable(seq_logp, totals)
+        return loss, seq_logp, totals
+
+    @staticmethod
+    def backward(ctx, g, _gs, _gt):
+        logits, labels32, adv, stats, totals = ctx.saved_tensors
+        N, tl, V = logits.shape
+        t = labels32.shape[1]
+        g = g.to(torch.float32).reshape(1).contiguous()   # a device scalar: the kernel reads it, the host never does
+        d = torch.empty(N, tl, V, device=logits.device, dtype=torch.float32)
+        with torch.cuda.device(logits.device):
+            _lib.call("care_reward_loss_bwd", _lib.ptr(logits), logits.stride(1), logits.stride(0), t, V, _lib.ptr(labels32),
+                      _lib.ptr(adv), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(totals), _lib.ptr(g), _lib.ptr(d), V, tl * V,
+                      tl, N * t, tag="reward_loss_bwd")
+        return d, None, None, None
+
+
+def self_critical_loss(logits, labels, advantages, acc: Optional[torch.Tensor] = None, return_aux: bool = False):
+    """The advantage-weighted log-likelihood of teacher-forced captions as a 0-dim fp32 device tensor under autograd.
+
+    logits fp32 [N, t, V] (or [N, t + 1, V]: the last position is skipped in place, as the language criterion does), labels
+    [N, t] with PAD = a dead position, advantages [N].  No label smoothing; an all-PAD batch gives 0 and a zero gradient.
+    acc (optional): 2 device doubles that accumulate (loss, n_live) for recorders.  return_aux: also the per-caption sum of
+    log-probabilities fp32 [N] and (sum adv logp, n_live) as 2 device doubles."""
+    if isinstance(logits, DeferredLogits):
+        raise NotImplementedError(
+            "`logits` is a DeferredLogits: the fused head (set_fused_head(True)) never materialises the [N, t, V] logits the "
+            "self-critical loss is taken over - call set_fused_head(False) on the module")
+    for what, t in (("logits", logits), ("labels", labels), ("advantages", advantages)):
+        _need_device(t, what)
+    if logits.dtype != torch.float32:
+        raise TypeError("`logits` must be fp32, got {}".format(logits.dtype))
+    if logits.dim() != 3 or labels.dim() != 2 or labels.shape[0] != logits.shape[0] or \
+            logits.shape[1] not in (labels.shape[1], labels.shape[1] + 1):
+        raise ValueError("logits [N, t (+ 1), V] and labels [N, t] expected, got {} and {}".format(tuple(logits.shape), tuple(labels.shape)))
+    if advantages.numel() != logits.shape[0]:
+        raise ValueError("`advantages` holds {} entries for N = {} captions".format(advantages.numel(), logits.shape[0]))
+    if logits.numel() == 0 or labels.numel() == 0:
+        raise ValueError("the loss of empty logits {} is undefined".format(tuple(logits.shape)))
+    if labels.device != logits.device or advantages.device != logits.device:
+        raise RuntimeError("logits are on `{}`, labels on `{}`, advantages on `{}`".format(logits.device, labels.device, advantages.device))
+    if acc is not None and (acc.dtype != torch.float64 or acc.numel() < 2 or acc.device != logits.device):
+        raise ValueError("`acc` must hold 2 float64 entries on {}".format(logits.device))
+    labels32 = labels.to(torch.int32).contiguous()
+    adv = advantages.detach().to(torch.float32).reshape(-1).contiguous()
+    loss, seq_logp, totals = _WeightedLogLik.apply(logits, labels32, adv, acc)
+    return (loss, seq_logp, totals) if return_aux else loss

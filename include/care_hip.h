@@ -994,6 +994,71 @@ int care_decode_chain_beam(const care_resident_layer* layers, int n_layers, cons
                            float* scores, int32_t* done, int32_t* nfin, float* fscore, int32_t* flen, int32_t* fhyp,
                            int fin_cap, void* scratch, int64_t scratch_bytes, int form, void* stream);
 
+/*
+ * Self-critical sequence training (care_amd/reward.py, care_amd/scst.py; csrc/reward.hip): the CIDEr-D of sampled captions
+ * as a reward, advantages against a baseline, and the advantage-weighted log-likelihood of the teacher-forced samples.  The
+ * reference only monitors the metric (opts.py `lr_monitor_metric` "CIDEr", computed by the Java / Python coco-caption
+ * tools on words); here it is the coco-caption CIDEr-D over integer token ids, restated in float64 in
+ * tests/cider_reference.py.  fp32 / double arithmetic in both libraries, no floating-point atomics, nothing synchronises.
+ *
+ * care_cider_score: out[r] (fp32) = the CIDEr-D of candidate r against the references of video[r].  Candidate r is
+ *   tokens[r * ld + col0 .. + min(length[r], width)) with ONE trailing `eos` dropped unless with_eos != 0; token ids are
+ *   taken modulo 2^16 and PAD (0) must not occur inside a caption.  An n-gram (n = 1..4) is one uint64 key, 16 bits a token,
+ *   the first token lowest, the orders below 4 zero-filled.  With tf the count of a key in a caption, df the number of videos
+ *   whose references hold it and N = n_videos:  w(g) = tf(g) (ln N - ln max(1, df(g)));  norm_n = sqrt(sum w^2) over a
+ *   caption's keys of order n;  for candidate h and reference r
+ *     sim_n = sum_{g in h, order n} min(w_h(g), w_r(g)) w_r(g),  divided by norm_n(h) norm_n(r) when both are non-zero,
+ *             times exp(-(len_h - len_r)^2 / 72);
+ *   out = 10 * (1 / 4) sum_n (1 / R) sum_{r < R} sim_n over the R references of the video.
+ *   The bank (a HOST struct of DEVICE arrays, built once by care_amd.reward.CiderBank):
+ *     corpus_keys [n_corpus] ascending (as uint64), corpus_lndf [n_corpus] = ln max(1, df) - a key that is absent has df 0;
+ *     ref_start [n_refs + 1]: reference i owns ref_keys / ref_w [ref_start[i], ref_start[i + 1]) - its unique keys ascending
+ *     and their weights; ref_norm [n_refs, 4]; ref_len [n_refs] (tokens, after the EOS rule); vid_start [n_videos + 1]:
+ *     video v owns the references [vid_start[v], vid_start[v + 1]); ln_n = ln N.
+ *   One workgroup of 256 per candidate: keys, tf and first-occurrence flags in LDS (all pairs), ln df by binary search in
+ *   corpus_keys, the references of the video dealt to the four waves round-robin, the lanes of a wave over the candidate's
+ *   unique keys with a binary search in the reference's keys.  Every sum is in double and in ONE order - the norms in key
+ *   order, a reference's sim_n by a scan in lane order, a wave's references in bank order, the waves in wave order - so a
+ *   row's bits do not depend on `rows` or on the row's place; rounded once to fp32.  Rows with length <= 0, an empty caption
+ *   or a video without references score 0.  A video[r] outside [0, n_videos) is never dereferenced: the row scores 0 and
+ *   *bad (optional, int32, ASSIGNED) counts such rows.
+ *   NULL tokens / length / video / out / bank or a NULL array in the bank, rows < 0, width < 1, width > 64, col0 < 0,
+ *   ld < col0 + width, n_videos < 1 -> CARE_EINVAL; a double / uint64 / int64 array that is not 8-byte aligned ->
+ *   CARE_EALIGN; before anything is launched.  rows == 0 is a no-op that returns 0.
+ * care_reward_advantage: adv [B, n] from reward [B, n] (fp32, every operation rounded on its own).  baseline [B] given
+ *   (the greedy caption's reward): adv = reward - baseline[b].  baseline NULL (leave-one-out, n >= 2 or CARE_EINVAL):
+ *     s = ((r_0 + r_1) + r_2) + ...,  base_j = (s - r_j) / (float)(n - 1),  adv_j = r_j - base_j.
+ *   stats (2 doubles, ASSIGNED): the mean over all B n entries of the reward and of the baseline that was subtracted, summed
+ *   in double in a fixed order (one workgroup).  NULL reward / adv / stats, B < 1 or n < 1 -> CARE_EINVAL; stats not 8-byte
+ *   aligned -> CARE_EALIGN.
+ * care_reward_loss_fwd: the logits and labels of care_lang_loss_fwd (same addressing: ld, seq_stride, rows_per_seq; label
+ *   PAD (0) or outside [0, V) = a dead row that is not read), adv fp32 [rows / rows_per_seq] one per sequence.  Per live row
+ *   rmax, lsum (kept apart for the backward) and logp = (x[y] - rmax) - lsum in fp32, 0 on dead rows; then ONE workgroup,
+ *   in double and a fixed order:  totals[0] = sum over live rows of adv logp, totals[1] = n_live,
+ *     *loss (DEVICE float) = -(totals[0] / n_live), 0 when n_live == 0;
+ *   seq_logp (optional, [rows / rows_per_seq]) = each sequence's sum of logp; acc (optional, 2 doubles) += loss, n_live.
+ * care_reward_loss_bwd: dlogits[s, p, c] = (float)(g adv[s] / n_live) (exp((x[c] - rmax) - lsum) - [c == y]) on live rows,
+ *   g = *g a DEVICE scalar, n_live = totals[1]; one read and one write per live row.  Dead rows, the positions rows_per_seq ..
+ *   seq_rows - 1 of every sequence and every row of a sequence whose adv is exactly 0 are zero-filled without reading their
+ *   logits.  dlogits is addressed as in care_lang_loss_bwd.
+ *   Both: the return codes of care_lang_loss_fwd / _bwd (eps apart); totals / acc not 8-byte aligned -> CARE_EALIGN.
+ */
+typedef struct care_cider_bank {
+  const uint64_t* corpus_keys; const double* corpus_lndf; int64_t n_corpus;
+  const uint64_t* ref_keys; const double* ref_w; const int64_t* ref_start; const double* ref_norm; const int32_t* ref_len;
+  const int32_t* vid_start; int32_t n_videos; int32_t n_refs;
+  double ln_n;
+} care_cider_bank;
+int care_cider_score(const int32_t* tokens, int ld, int col0, int width, const int32_t* length, const int32_t* video,
+                     int rows, int with_eos, int eos, const care_cider_bank* bank, float* out, int32_t* bad, void* stream);
+int care_reward_advantage(const float* reward, const float* baseline, int B, int n, float* adv, double* stats, void* stream);
+int care_reward_loss_fwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V, const int32_t* labels,
+                         const float* adv, float* rmax, float* lsum, float* logp, double* totals, float* loss, float* seq_logp,
+                         double* acc, int rows, void* stream);
+int care_reward_loss_bwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V, const int32_t* labels,
+                         const float* adv, const float* rmax, const float* lsum, const double* totals, const float* g,
+                         float* dlogits, int64_t ldd, int64_t dseq_stride, int seq_rows, int rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
