@@ -58,23 +58,40 @@ def _rows_f32(t: torch.Tensor) -> torch.Tensor:
     return t if t.stride(-1) == 1 else t.contiguous()
 
 
+def _seq_rows(logits: torch.Tensor, t: int):
+    """Logits [N, t (+ 1), V] as the row kernels address them (csrc/vocab_row.h): whole sequences at one stride, rows at
+    another, so [N, t + 1, V] is walked in place with its last position skipped; any other layout is made contiguous.
+    Returns the logits to keep for the backward and the leading arguments of the four entry points
+    (logits, ld, seq_stride, rows_per_seq, V)."""
+    V = logits.shape[2]
+    if logits.stride(2) != 1 or logits.stride(1) < V or logits.stride(0) < t * logits.stride(1):
+        logits = logits.contiguous()
+    return logits, (ptr(logits), logits.stride(1), logits.stride(0), t, V)
+
+
+def _seq_rows_grad(logits: torch.Tensor, t: int):
+    """For the backward, on the logits `_seq_rows` returned: a contiguous gradient [N, tl, V] (the kernels write every row of
+    it), the same leading arguments, and the trailing ones of the two backward entry points
+    (dlogits, ldd, dseq_stride, seq_rows, rows)."""
+    N, tl, V = logits.shape
+    d = torch.empty(N, tl, V, device=logits.device, dtype=torch.float32)
+    return d, _seq_rows(logits, t)[1], (ptr(d), V, tl * V, tl, N * t)
+
+
 class _LangLoss(torch.autograd.Function):
     """sum over the non-PAD label positions of (1 - eps) NLL + eps (lse - mean x) (crit_lang.py:57-71)."""
 
     @staticmethod
     def forward(ctx, logits, labels32, eps, acc):
-        N, tl, V = logits.shape
-        t = labels32.shape[1]
-        # whole sequences at one stride, rows at another: [N, t + 1, V] is walked in place, its last position skipped
-        if logits.stride(2) != 1 or logits.stride(1) < V or logits.stride(0) < t * logits.stride(1):
-            logits = logits.contiguous()
+        N, t = logits.shape[0], labels32.shape[1]
+        logits, src = _seq_rows(logits, t)
         rows, dev = N * t, logits.device
         stats = torch.empty(5, rows, device=dev, dtype=torch.float32)   # lse, max, log sum exp(x - max), logp, row_loss
         pred = torch.empty(rows, device=dev, dtype=torch.int32)
         sums = torch.empty(2, device=dev, dtype=torch.float32)
         counts = torch.empty(3, device=dev, dtype=torch.int32)
-        call("care_lang_loss_fwd", ptr(logits), logits.stride(1), logits.stride(0), t, V, ptr(labels32), eps, ptr(stats[0]),
-             ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(pred), ptr(stats[4]), ptr(sums), ptr(counts), ptr(acc), rows)
+        call("care_lang_loss_fwd", *src, ptr(labels32), eps, ptr(stats[0]), ptr(stats[1]), ptr(stats[2]), ptr(stats[3]), ptr(pred),
+             ptr(stats[4]), ptr(sums), ptr(counts), ptr(acc), rows)
         ctx.save_for_backward(logits, labels32, stats)
         ctx.eps = eps
         pred = pred.view(N, t)
@@ -84,12 +101,10 @@ class _LangLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _gp, _gc):
         logits, labels32, stats = ctx.saved_tensors
-        N, tl, V = logits.shape
         t = labels32.shape[1]
         g = g.to(torch.float32).reshape(1).contiguous()   # a device scalar: the kernel reads it, the host never does
-        d = torch.empty(N, tl, V, device=logits.device, dtype=torch.float32)
-        call("care_lang_loss_bwd", ptr(logits), logits.stride(1), logits.stride(0), t, V, ptr(labels32), ptr(stats[1]), ptr(stats[2]), ctx.eps,
-             ptr(g), ptr(d), V, tl * V, tl, N * t)
+        d, src, dst = _seq_rows_grad(logits, t)
+        call("care_lang_loss_bwd", *src, ptr(labels32), ptr(stats[1]), ptr(stats[2]), ctx.eps, ptr(g), *dst)
         return d, None, None, None
 
 

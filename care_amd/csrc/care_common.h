@@ -82,10 +82,37 @@ __device__ __forceinline__ float care_wave_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ int care_wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 __device__ __forceinline__ float care_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// arg-max with the lowest index on ties: (best, bi) takes (v, c) when v is larger, or equal at a lower index ...
+__device__ __forceinline__ void care_argmax_take(float& best, int& bi, float v, int c) {
+  if (v > best || (v == best && c < bi)) { best = v; bi = c; }
+}
+
+// ... and over the wave, in xor steps; every lane gets it
+__device__ __forceinline__ void care_wave_argmax(float& best, int& bi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(best, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    care_argmax_take(best, bi, ov, oi);
+  }
+}
+
+// The label-smoothed loss of one row of V logits (misc/Crit/crit_lang.py:57-71): lp = log p[label], L = log sum exp x,
+// sx = sum x.  For loss.hip and head_loss.hip, which compile with floating-point contraction on.
+__device__ __forceinline__ float care_smoothed_row_loss(float eps, float lp, float L, float sx, int V) {
+  return (1.f - eps) * (-lp) + eps * (L - sx / (float)V);
 }
 
 // Wave-wide maximum through the DPP data path: an inclusive max-scan along each row of 16 lanes

@@ -17,12 +17,6 @@ namespace {
 
 #define HST ((hipStream_t)stream)
 
-__device__ __forceinline__ int hl_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One workgroup: thread t owns the positions t per .. t per + per - 1, counts its live ones, an exclusive scan over the
 // threads gives its first output slot - ascending order by construction.
 __global__ __launch_bounds__(1024) void head_live_rows_kernel(const int32_t* labels, int rows, int t, int seq_rows, int V,
@@ -43,7 +37,7 @@ __global__ __launch_bounds__(1024) void head_live_rows_kernel(const int32_t* lab
     const int v = __shfl_up(inc, o, 64);
     if (lane >= o) inc += v;
   }
-  bad = hl_wave_sum_i(bad);
+  bad = care_wave_sum_i(bad);
   if (lane == 63) wl[wave] = inc;
   if (lane == 0) wb[wave] = bad;
   __syncthreads();
@@ -76,17 +70,8 @@ __global__ __launch_bounds__(256) void head_finish_kernel(const float* pmax, con
   const int64_t o = (int64_t)i * parts;
   float best = -INFINITY;
   int bi = 0x7fffffff;
-  for (int k = lane; k < parts; k += 64) {
-    const float v = pmax[o + k];
-    const int c = pidx[o + k];
-    if (v > best || (v == best && c < bi)) { best = v; bi = c; }
-  }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    const float ov = __shfl_xor(best, s, 64);
-    const int oi = __shfl_xor(bi, s, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
+  for (int k = lane; k < parts; k += 64) care_argmax_take(best, bi, pmax[o + k], pidx[o + k]);
+  care_wave_argmax(best, bi);
   float s = 0.f, sx = 0.f, lv = -INFINITY;
   for (int k = lane; k < parts; k += 64) {
     s += psum[o + k] * expf(pmax[o + k] - best);
@@ -105,7 +90,7 @@ __global__ __launch_bounds__(256) void head_finish_kernel(const float* pmax, con
     lsum[r] = ls;
     logp[r] = lp;
     pred[r] = bi;
-    row_loss[r] = (1.f - eps) * (-lp) + eps * (L - sx / (float)V);
+    row_loss[r] = care_smoothed_row_loss(eps, lp, L, sx, V);
     rmax_c[i] = best;
     lsum_c[i] = ls;
   }

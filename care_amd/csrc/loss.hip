@@ -7,39 +7,16 @@
 // backward reads it once more and writes the gradient: three sweeps of the live rows in all.  Rows whose label is PAD - most of
 // them with captions of ~8 of 29 positions - are never read, and only zero-filled in the backward.
 //
-// A row starts at any 4-byte phase (ld = V = 10547 is odd): every sweep peels `head` = 0..3 scalars up to the next 16-byte
-// boundary, walks float4s, and ends with `tail` = 0..3 scalars.  No floating-point atomics: per-row results, then a
-// one-workgroup reduce that adds them in a fixed order.
-#include "care_common.h"
+// The sweeps of a row - its head / float4 / tail span, the register-resident and the re-reading forward, the sum of exponentials,
+// the meets of the four waves, the writer of a gradient row - are vocab_row.h's, shared with reward.hip; here are the visitor
+// (arg-max + sum x), the smoothed row loss and the gradient.  No floating-point atomics: per-row results, then a one-workgroup
+// reduce that adds them in a fixed order.
+#include "vocab_row.h"
 
 namespace {
 
 #define LST ((hipStream_t)stream)
-constexpr int LT = 256;  // threads of a row workgroup (4 waves)
-
-// x[0 .. V) as head scalars, n4 aligned float4s from x + head, tail scalars
-__device__ __forceinline__ void row_span(const float* x, int V, int& head, int& n4, int& tail) {
-  head = (int)((4u - (unsigned)(((uintptr_t)x >> 2) & 3u)) & 3u);
-  if (head > V) head = V;
-  n4 = (V - head) >> 2;
-  tail = V - head - 4 * n4;
-}
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// sum over the 4 waves of a row workgroup, in wave order; every thread gets it
-__device__ __forceinline__ float block_sum4(float v, float* sm) {
-  v = care_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float t = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-  __syncthreads();
-  return t;
-}
+constexpr int LT = CARE_ROW_THREADS;
 
 // forward of one row per workgroup.  NV4 > 0: the row's float4s live in registers (V <= 1024 NV4); NV4 == 0: the
 // re-reading form for any V (the second sweep finds the row in the L2).
@@ -49,84 +26,25 @@ __global__ __launch_bounds__(LT) void lang_loss_fwd_kernel(const float* logits, 
                                                            float* lsum, float* logp, int32_t* pred, float* row_loss) {
   __shared__ float sm[4];
   __shared__ int si[4];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = blockIdx.x, tid = threadIdx.x;
   const int y = labels[r];
   if (y <= 0 || y >= V) {  // PAD, or a label outside [0, V) (counted by the reduce): not read, contributes nothing
     if (tid == 0) { lse[r] = 0.f; rmax[r] = 0.f; lsum[r] = 0.f; logp[r] = 0.f; pred[r] = 0; row_loss[r] = 0.f; }
     return;
   }
   const float* x = logits + (int64_t)(r / rows_per_seq) * seq_stride + (int64_t)(r % rows_per_seq) * ld;
-  int head, n4, tail;
-  row_span(x, V, head, n4, tail);
-  const float4* xb = reinterpret_cast<const float4*>(x + head);
-
+  // arg-max of the row, lowest index on ties, and the sum of its values
   float best = -INFINITY, sx = 0.f;
   int bi = 0x7fffffff;
-#define SEE(VAL, COL)                                              \
-  {                                                                \
-    const float v_ = (VAL);                                        \
-    const int c_ = (COL);                                          \
-    if (v_ > best || (v_ == best && c_ < bi)) { best = v_; bi = c_; } \
-    sx += v_;                                                      \
-  }
-  // the (at most 6) scalars around the float4 body: thread t < head owns x[t], the next `tail` threads the row's end
-  int ec = -1;
-  if (tid < head) ec = tid;
-  else if (tid < head + tail) ec = head + 4 * n4 + (tid - head);
-  float ev = 0.f;
-  if (ec >= 0) { ev = x[ec]; SEE(ev, ec); }
-
-  float4 v[NV4 > 0 ? NV4 : 1];
-  if (NV4 > 0) {
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int j = tid + i * LT;
-      if (j < n4) v[i] = xb[j];
-    }
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int j = tid + i * LT, c0 = head + 4 * j;
-      if (j < n4) { SEE(v[i].x, c0); SEE(v[i].y, c0 + 1); SEE(v[i].z, c0 + 2); SEE(v[i].w, c0 + 3); }
-    }
-  } else {
-    for (int j = tid; j < n4; j += LT) {
-      const float4 q = xb[j];
-      const int c0 = head + 4 * j;
-      SEE(q.x, c0); SEE(q.y, c0 + 1); SEE(q.z, c0 + 2); SEE(q.w, c0 + 3);
-    }
-  }
-#undef SEE
-  // arg-max of the row, lowest index on ties
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
-  }
-  if (lane == 0) { sm[wave] = best; si[wave] = bi; }
-  __syncthreads();
-  best = sm[0]; bi = si[0];
-#pragma unroll
-  for (int w = 1; w < 4; ++w)
-    if (sm[w] > best || (sm[w] == best && si[w] < bi)) { best = sm[w]; bi = si[w]; }
-  __syncthreads();
-  sx = block_sum4(sx, sm);
-
-  float s = 0.f;
-  if (ec >= 0) s += expf(ev - best);
-  if (NV4 > 0) {
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int j = tid + i * LT;
-      if (j < n4) s += (expf(v[i].x - best) + expf(v[i].y - best)) + (expf(v[i].z - best) + expf(v[i].w - best));
-    }
-  } else {
-    for (int j = tid; j < n4; j += LT) {
-      const float4 q = xb[j];
-      s += (expf(q.x - best) + expf(q.y - best)) + (expf(q.z - best) + expf(q.w - best));
-    }
-  }
-  s = block_sum4(s, sm);
+  auto see = [&](float v, int c) {
+    care_argmax_take(best, bi, v, c);
+    sx += v;
+  };
+  care_row<NV4> row;
+  row.sweep(x, V, see, [&](const float4& q, int c0) { see(q.x, c0); see(q.y, c0 + 1); see(q.z, c0 + 2); see(q.w, c0 + 3); });
+  care_block_argmax4(best, bi, sm, si);
+  sx = care_block_sum4(sx, sm);
+  const float s = care_block_sum4(row.sum_exp(best), sm);
   if (tid == 0) {
     const float ls = logf(s), L = best + ls;
     const float lp = (x[y] - best) - ls;
@@ -135,7 +53,7 @@ __global__ __launch_bounds__(LT) void lang_loss_fwd_kernel(const float* logits, 
     lsum[r] = ls;
     logp[r] = lp;
     pred[r] = bi;
-    row_loss[r] = (1.f - eps) * (-lp) + eps * (L - sx / (float)V);
+    row_loss[r] = care_smoothed_row_loss(eps, lp, L, sx, V);
   }
 }
 
@@ -160,7 +78,7 @@ __global__ __launch_bounds__(1024) void lang_loss_reduce_kernel(const float* row
     }
   }
   a = care_wave_sum(a); b = care_wave_sum(b);
-  h = wave_sum_i(h); w = wave_sum_i(w); bad = wave_sum_i(bad);
+  h = care_wave_sum_i(h); w = care_wave_sum_i(w); bad = care_wave_sum_i(bad);
   if (lane == 0) { fa[wave] = a; fb[wave] = b; ih[wave] = h; iw[wave] = w; ib[wave] = bad; }
   __syncthreads();
   if (tid == 0) {
@@ -173,52 +91,25 @@ __global__ __launch_bounds__(1024) void lang_loss_reduce_kernel(const float* row
 }
 
 // backward: one workgroup per row of dlogits (sequence s, position p < seq_rows); live rows one read + one write, the
-// others (PAD, bad label, p >= rows_per_seq) a zero fill.  The float4 walk is aligned on the STORE side; the loads are
-// float4s too when the logits row has the same 16-byte phase (always so when both tensors are contiguous with one
-// leading dimension), four scalars otherwise.
+// others (PAD, bad label, p >= rows_per_seq) a zero fill (vocab_row.h: care_row_zero, care_row_map).
 __global__ __launch_bounds__(LT) void lang_loss_bwd_kernel(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq,
                                                            int V, const int32_t* labels, const float* rmax, const float* lsum,
                                                            float eps, const float* g, float* dlogits, int64_t ldd,
                                                            int64_t dseq_stride, int seq_rows) {
-  const int tid = threadIdx.x;
   const int s = blockIdx.x / seq_rows, p = blockIdx.x % seq_rows;
   float* d = dlogits + (int64_t)s * dseq_stride + (int64_t)p * ldd;
   int y = 0, r = 0;
   if (p < rows_per_seq) { r = s * rows_per_seq + p; y = labels[r]; }
-  int head, n4, tail;
-  row_span(d, V, head, n4, tail);
-  float4* db = reinterpret_cast<float4*>(d + head);
-  int ec = -1;
-  if (tid < head) ec = tid;
-  else if (tid < head + tail) ec = head + 4 * n4 + (tid - head);
+  const care_row_span sp = care_row_span_of(d, V);
   if (y <= 0 || y >= V) {
-    if (ec >= 0) d[ec] = 0.f;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j = tid; j < n4; j += LT) db[j] = z;
+    care_row_zero(d, sp);
     return;
   }
   const float* x = logits + (int64_t)s * seq_stride + (int64_t)p * ld;
   // softmax as exp((x - max) - log sum exp(x - max)): x - max is exact for the columns that carry the probability, where
   // x - lse would round at an ulp of |lse| (a row of logits around 5e3: 2e-4 of every probability)
   const float m = rmax[r], ls = lsum[r], gg = *g, sub = eps / (float)V, hot = 1.f - eps;
-#define GRAD(VAL, COL) (gg * ((expf(((VAL) - m) - ls) - sub) - ((COL) == y ? hot : 0.f)))
-  if (ec >= 0) d[ec] = GRAD(x[ec], ec);
-  const bool same_phase = ((((uintptr_t)x) ^ ((uintptr_t)d)) & 15u) == 0;
-  if (same_phase) {
-    const float4* xb = reinterpret_cast<const float4*>(x + head);
-#pragma unroll 4
-    for (int j = tid; j < n4; j += LT) {
-      const float4 q = xb[j];
-      const int c0 = head + 4 * j;
-      db[j] = make_float4(GRAD(q.x, c0), GRAD(q.y, c0 + 1), GRAD(q.z, c0 + 2), GRAD(q.w, c0 + 3));
-    }
-  } else {
-    for (int j = tid; j < n4; j += LT) {
-      const int c0 = head + 4 * j;
-      db[j] = make_float4(GRAD(x[c0], c0), GRAD(x[c0 + 1], c0 + 1), GRAD(x[c0 + 2], c0 + 2), GRAD(x[c0 + 3], c0 + 3));
-    }
-  }
-#undef GRAD
+  care_row_map(x, d, sp, [=](float v, int c) { return gg * ((expf((v - m) - ls) - sub) - (c == y ? hot : 0.f)); });
 }
 
 // ------------------------------------------------------------------ concept BCE: one wave per clip
@@ -263,7 +154,7 @@ __global__ __launch_bounds__(LT) void sum_reduce_kernel(const float* x, int n, f
   __shared__ float sm[4];
   float a = 0.f;
   for (int i = threadIdx.x; i < n; i += LT) a += x[i];
-  a = block_sum4(a, sm);
+  a = care_block_sum4(a, sm);
   if (threadIdx.x == 0) {
     sums[0] = a;
     if (acc) acc[0] += (double)a;
@@ -276,10 +167,10 @@ extern "C" int care_lang_loss_fwd(const float* logits, int64_t ld, int64_t seq_s
                                   const int32_t* labels, float eps, float* lse, float* rmax, float* lsum, float* logp,
                                   int32_t* pred, float* row_loss, float* sums, int32_t* counts, double* acc, int rows,
                                   void* stream) {
-  if (!logits || !labels || !lse || !rmax || !lsum || !logp || !pred || !row_loss || !sums || !counts || rows <= 0 || V <= 0 || rows_per_seq <= 0)
-    return CARE_EINVAL;
-  if (ld < V || seq_stride < (int64_t)rows_per_seq * ld || !(eps >= 0.f && eps <= 1.f)) return CARE_ESHAPE;
-  if (((uintptr_t)logits & 3u) || (acc && ((uintptr_t)acc & 7u))) return CARE_EALIGN;
+  const int bad = care_row_check_fwd(logits && labels && lse && rmax && lsum && logp && pred && row_loss && sums && counts, logits, ld,
+                                     seq_stride, rows_per_seq, V, rows, eps >= 0.f && eps <= 1.f,
+                                     !(acc && ((uintptr_t)acc & 7u)));
+  if (bad) return bad;
 #define FWD_LAUNCH(N) hipLaunchKernelGGL(lang_loss_fwd_kernel<N>, dim3(rows), dim3(LT), 0, LST, logits, ld, seq_stride, rows_per_seq, V, labels, eps, lse, rmax, lsum, logp, pred, row_loss)
   if (V <= 4096) FWD_LAUNCH(4);
   else if (V <= 8192) FWD_LAUNCH(8);
@@ -302,14 +193,11 @@ extern "C" int care_lang_loss_reduce(const float* row_loss, const float* logp, c
 extern "C" int care_lang_loss_bwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V,
                                   const int32_t* labels, const float* rmax, const float* lsum, float eps, const float* g,
                                   float* dlogits, int64_t ldd, int64_t dseq_stride, int seq_rows, int rows, void* stream) {
-  if (!logits || !labels || !rmax || !lsum || !g || !dlogits || rows <= 0 || V <= 0 || rows_per_seq <= 0) return CARE_EINVAL;
-  if (ld < V || ldd < V || seq_rows < rows_per_seq || rows % rows_per_seq != 0 || seq_stride < (int64_t)rows_per_seq * ld ||
-      dseq_stride < (int64_t)seq_rows * ldd || !(eps >= 0.f && eps <= 1.f))
-    return CARE_ESHAPE;
-  if (((uintptr_t)logits & 3u) || ((uintptr_t)dlogits & 3u)) return CARE_EALIGN;
-  const int64_t grid = (int64_t)(rows / rows_per_seq) * seq_rows;
-  if (grid > 0x7fffffff) return CARE_ESHAPE;
-  hipLaunchKernelGGL(lang_loss_bwd_kernel, dim3((unsigned)grid), dim3(LT), 0, LST, logits, ld, seq_stride, rows_per_seq, V, labels, rmax,
+  unsigned grid = 0;
+  const int bad = care_row_check_bwd(logits && labels && rmax && lsum && g && dlogits, logits, ld, seq_stride, rows_per_seq, V, dlogits,
+                                     ldd, dseq_stride, seq_rows, rows, eps >= 0.f && eps <= 1.f, true, &grid);
+  if (bad) return bad;
+  hipLaunchKernelGGL(lang_loss_bwd_kernel, dim3(grid), dim3(LT), 0, LST, logits, ld, seq_stride, rows_per_seq, V, labels, rmax,
                      lsum, eps, g, dlogits, ldd, dseq_stride, seq_rows);
   return care_launch_status();
 }

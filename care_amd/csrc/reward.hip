@@ -9,25 +9,20 @@
 // Every sum is in double and in one order (the norms in key order, a reference's terms by a scan in lane order, a wave's
 // references in bank order, the waves in wave order): a row's bits depend on the row alone.  No atomics.
 //
-// The loss: the row kernels of csrc/loss.hip without the arg-max and the label-smoothing mean - a live row is read once in the
-// forward (in registers while V <= 12288) and once in the backward - and the weight of a row is its sequence's advantage over
-// the number of live positions, which stays on the device.
-#include "care_common.h"
+// The loss: the row sweeps of csrc/vocab_row.h, which the language loss runs too, with a plain maximum as the visitor - a live
+// row is read once in the forward (in registers while V <= 12288) and once in the backward - and the weight of a row is its
+// sequence's advantage over the number of live positions, which stays on the device.
+#include "vocab_row.h"
 
-// the advantage has the bits of torch's elementwise fp32 operations: nothing is fused
+// the advantage has the bits of torch's elementwise fp32 operations: nothing is fused (vocab_row.h, above this line, holds
+// nothing that could be)
 #pragma clang fp contract(off)
 
 namespace {
 
 #define RST ((hipStream_t)stream)
-constexpr int RT = 256;          // threads of a workgroup (4 waves)
-constexpr int CID_MAXLEN = 64;   // tokens of a caption
-
-__device__ __forceinline__ int rw_wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
+constexpr int RT = CARE_ROW_THREADS;   // threads of a workgroup (4 waves)
+constexpr int CID_MAXLEN = 64;         // tokens of a caption
 
 // the wave's sum by an inclusive scan in lane order (Hillis-Steele: lane l ends with v_0 + .. + v_l in ONE tree of additions),
 // lane 63's total to every lane.  All 64 lanes must be active.
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(RT) void cider_bad_kernel(const int32_t* video, int
     const int v = video[r];
     c += (v < 0 || v >= n_videos) ? 1 : 0;
   }
-  c = rw_wave_sum_i(c);
+  c = care_wave_sum_i(c);
   if ((threadIdx.x & 63) == 0) si[threadIdx.x >> 6] = c;
   __syncthreads();
   if (threadIdx.x == 0) *bad = (si[0] + si[1]) + (si[2] + si[3]);
@@ -231,78 +226,27 @@ __global__ __launch_bounds__(RT) void reward_advantage_kernel(const float* rewar
 }
 
 // ------------------------------------------------------------------ the weighted log-likelihood
-// x[0 .. V) as head scalars, n4 aligned float4s from x + head, tail scalars (csrc/loss.hip)
-__device__ __forceinline__ void rw_row_span(const float* x, int V, int& head, int& n4, int& tail) {
-  head = (int)((4u - (unsigned)(((uintptr_t)x >> 2) & 3u)) & 3u);
-  if (head > V) head = V;
-  n4 = (V - head) >> 2;
-  tail = V - head - 4 * n4;
-}
-
 // forward of one row per workgroup.  NV4 > 0: the row's float4s live in registers (V <= 1024 NV4); NV4 == 0: the re-reading
 // form for any V.
 template <int NV4>
 __global__ __launch_bounds__(RT) void reward_loss_fwd_kernel(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq,
                                                              int V, const int32_t* labels, float* rmax, float* lsum, float* logp) {
   __shared__ float sm[4];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = blockIdx.x, tid = threadIdx.x;
   const int y = labels[r];
   if (y <= 0 || y >= V) {   // PAD or a label outside [0, V): not read
     if (tid == 0) { rmax[r] = 0.f; lsum[r] = 0.f; logp[r] = 0.f; }
     return;
   }
   const float* x = logits + (int64_t)(r / rows_per_seq) * seq_stride + (int64_t)(r % rows_per_seq) * ld;
-  int head, n4, tail;
-  rw_row_span(x, V, head, n4, tail);
-  const float4* xb = reinterpret_cast<const float4*>(x + head);
-  int ec = -1;
-  if (tid < head) ec = tid;
-  else if (tid < head + tail) ec = head + 4 * n4 + (tid - head);
-  float best = -INFINITY, ev = 0.f;
-  if (ec >= 0) { ev = x[ec]; best = ev; }
-  float4 v[NV4 > 0 ? NV4 : 1];
-  if (NV4 > 0) {
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int j = tid + i * RT;
-      if (j < n4) v[i] = xb[j];
-    }
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int j = tid + i * RT;
-      if (j < n4) best = fmaxf(fmaxf(best, fmaxf(v[i].x, v[i].y)), fmaxf(v[i].z, v[i].w));
-    }
-  } else {
-    for (int j = tid; j < n4; j += RT) {
-      const float4 q = xb[j];
-      best = fmaxf(fmaxf(best, fmaxf(q.x, q.y)), fmaxf(q.z, q.w));
-    }
-  }
-  best = care_wave_max(best);
-  if (lane == 0) sm[wave] = best;
-  __syncthreads();
-  best = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-  __syncthreads();
-
-  float s = 0.f;
-  if (ec >= 0) s += expf(ev - best);
-  if (NV4 > 0) {
-#pragma unroll
-    for (int i = 0; i < NV4; ++i) {
-      const int j = tid + i * RT;
-      if (j < n4) s += (expf(v[i].x - best) + expf(v[i].y - best)) + (expf(v[i].z - best) + expf(v[i].w - best));
-    }
-  } else {
-    for (int j = tid; j < n4; j += RT) {
-      const float4 q = xb[j];
-      s += (expf(q.x - best) + expf(q.y - best)) + (expf(q.z - best) + expf(q.w - best));
-    }
-  }
-  s = care_wave_sum(s);
-  if (lane == 0) sm[wave] = s;
-  __syncthreads();
+  float best = -INFINITY;
+  care_row<NV4> row;
+  row.sweep(x, V, [&](float v, int) { best = v; },
+            [&](const float4& q, int) { best = fmaxf(fmaxf(best, fmaxf(q.x, q.y)), fmaxf(q.z, q.w)); });
+  best = care_block_max4(best, sm);
+  const float s = care_block_sum4(row.sum_exp(best), sm);
   if (tid == 0) {
-    const float ls = logf((sm[0] + sm[1]) + (sm[2] + sm[3]));
+    const float ls = logf(s);
     rmax[r] = best;
     lsum[r] = ls;
     logp[r] = (x[y] - best) - ls;
@@ -328,7 +272,7 @@ __global__ __launch_bounds__(1024) void reward_loss_reduce_kernel(const float* l
     }
   }
   a = rw_wave_scan_total(a);
-  c = rw_wave_sum_i(c);
+  c = care_wave_sum_i(c);
   if (lane == 0) { sa[wave] = a; sc[wave] = c; }
   __syncthreads();
   if (tid == 0) {
@@ -351,50 +295,25 @@ __global__ __launch_bounds__(1024) void reward_loss_reduce_kernel(const float* l
 }
 
 // backward: one workgroup per row of dlogits (sequence s, position p < seq_rows); live rows of a sequence with a non-zero
-// advantage one read + one write, the others a zero fill (csrc/loss.hip, lang_loss_bwd_kernel)
+// advantage one read + one write, the others a zero fill (vocab_row.h: care_row_zero, care_row_map)
 __global__ __launch_bounds__(RT) void reward_loss_bwd_kernel(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq,
                                                              int V, const int32_t* labels, const float* adv, const float* rmax,
                                                              const float* lsum, const double* totals, const float* g,
                                                              float* dlogits, int64_t ldd, int64_t dseq_stride, int seq_rows) {
-  const int tid = threadIdx.x;
   const int s = blockIdx.x / seq_rows, p = blockIdx.x % seq_rows;
   float* d = dlogits + (int64_t)s * dseq_stride + (int64_t)p * ldd;
   int y = 0, r = 0;
   float ad = 0.f;
   if (p < rows_per_seq) { r = s * rows_per_seq + p; y = labels[r]; ad = adv[s]; }
-  int head, n4, tail;
-  rw_row_span(d, V, head, n4, tail);
-  float4* db = reinterpret_cast<float4*>(d + head);
-  int ec = -1;
-  if (tid < head) ec = tid;
-  else if (tid < head + tail) ec = head + 4 * n4 + (tid - head);
+  const care_row_span sp = care_row_span_of(d, V);
   if (y <= 0 || y >= V || ad == 0.f) {
-    if (ec >= 0) d[ec] = 0.f;
-    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int j = tid; j < n4; j += RT) db[j] = z;
+    care_row_zero(d, sp);
     return;
   }
   const float* x = logits + (int64_t)s * seq_stride + (int64_t)p * ld;
   const float m = rmax[r], ls = lsum[r];
   const float cf = (float)((double)(*g) * (double)ad / totals[1]);   // (a live row: n_live >= 1)
-#define GRAD(VAL, COL) (cf * (expf(((VAL) - m) - ls) - ((COL) == y ? 1.f : 0.f)))
-  if (ec >= 0) d[ec] = GRAD(x[ec], ec);
-  const bool same_phase = ((((uintptr_t)x) ^ ((uintptr_t)d)) & 15u) == 0;
-  if (same_phase) {
-    const float4* xb = reinterpret_cast<const float4*>(x + head);
-#pragma unroll 4
-    for (int j = tid; j < n4; j += RT) {
-      const float4 q = xb[j];
-      const int c0 = head + 4 * j;
-      db[j] = make_float4(GRAD(q.x, c0), GRAD(q.y, c0 + 1), GRAD(q.z, c0 + 2), GRAD(q.w, c0 + 3));
-    }
-  } else {
-    for (int j = tid; j < n4; j += RT) {
-      const int c0 = head + 4 * j;
-      db[j] = make_float4(GRAD(x[c0], c0), GRAD(x[c0 + 1], c0 + 1), GRAD(x[c0 + 2], c0 + 2), GRAD(x[c0 + 3], c0 + 3));
-    }
-  }
-#undef GRAD
+  care_row_map(x, d, sp, [=](float v, int c) { return cf * (expf((v - m) - ls) - (c == y ? 1.f : 0.f)); });
 }
 
 inline bool rw_mis8(const void* p) { return (((uintptr_t)p) & 7u) != 0; }
@@ -435,10 +354,11 @@ extern "C" int care_reward_advantage(const float* reward, const float* baseline,
 extern "C" int care_reward_loss_fwd(const float* logits, int64_t ld, int64_t seq_stride, int rows_per_seq, int V,
                                     const int32_t* labels, const float* adv, float* rmax, float* lsum, float* logp, double* totals,
                                     float* loss, float* seq_logp, double* acc, int rows, void* stream) {
-  if (!logits || !labels || !adv || !rmax || !lsum || !logp || !totals || !loss || rows <= 0 || V <= 0 || rows_per_seq <= 0)
-    return CARE_EINVAL;
-  if (ld < V || seq_stride < (int64_t)rows_per_seq * ld || rows % rows_per_seq != 0) return CARE_ESHAPE;
-  if (((uintptr_t)logits & 3u) || rw_mis8(totals) || (acc && rw_mis8(acc))) return CARE_EALIGN;
+  // (whole sequences only; without a rows_per_seq to divide by the call is CARE_EINVAL whatever stands here)
+  const int bad = care_row_check_fwd(logits && labels && adv && rmax && lsum && logp && totals && loss, logits, ld, seq_stride,
+                                     rows_per_seq, V, rows, rows_per_seq > 0 && rows % rows_per_seq == 0,
+                                     !(rw_mis8(totals) || (acc && rw_mis8(acc))));
+  if (bad) return bad;
 #define FWD_LAUNCH(N) hipLaunchKernelGGL(reward_loss_fwd_kernel<N>, dim3(rows), dim3(RT), 0, RST, logits, ld, seq_stride, rows_per_seq, V, labels, rmax, lsum, logp)
   if (V <= 4096) FWD_LAUNCH(4);
   else if (V <= 12288) FWD_LAUNCH(12);
@@ -453,15 +373,11 @@ extern "C" int care_reward_loss_bwd(const float* logits, int64_t ld, int64_t seq
                                     const int32_t* labels, const float* adv, const float* rmax, const float* lsum,
                                     const double* totals, const float* g, float* dlogits, int64_t ldd, int64_t dseq_stride,
                                     int seq_rows, int rows, void* stream) {
-  if (!logits || !labels || !adv || !rmax || !lsum || !totals || !g || !dlogits || rows <= 0 || V <= 0 || rows_per_seq <= 0)
-    return CARE_EINVAL;
-  if (ld < V || ldd < V || seq_rows < rows_per_seq || rows % rows_per_seq != 0 || seq_stride < (int64_t)rows_per_seq * ld ||
-      dseq_stride < (int64_t)seq_rows * ldd)
-    return CARE_ESHAPE;
-  if (((uintptr_t)logits & 3u) || ((uintptr_t)dlogits & 3u) || rw_mis8(totals)) return CARE_EALIGN;
-  const int64_t grid = (int64_t)(rows / rows_per_seq) * seq_rows;
-  if (grid > 0x7fffffff) return CARE_ESHAPE;
-  hipLaunchKernelGGL(reward_loss_bwd_kernel, dim3((unsigned)grid), dim3(RT), 0, RST, logits, ld, seq_stride, rows_per_seq, V, labels,
+  unsigned grid = 0;
+  const int bad = care_row_check_bwd(logits && labels && adv && rmax && lsum && totals && g && dlogits, logits, ld, seq_stride,
+                                     rows_per_seq, V, dlogits, ldd, dseq_stride, seq_rows, rows, true, !rw_mis8(totals), &grid);
+  if (bad) return bad;
+  hipLaunchKernelGGL(reward_loss_bwd_kernel, dim3(grid), dim3(RT), 0, RST, logits, ld, seq_stride, rows_per_seq, V, labels,
                      adv, rmax, lsum, totals, g, dlogits, ldd, dseq_stride, seq_rows);
   return care_launch_status();
 }

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from .constants import EOS, PAD
-from .criterion import DeferredLogits
+from .criterion import DeferredLogits, _seq_rows, _seq_rows_grad
 
 __all__ = ["CiderBank", "reward_advantage", "self_critical_loss", "pack_ngrams", "MAX_CAPTION"]
 
@@ -225,20 +225,17 @@ class _WeightedLogLik(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits, labels32, adv, acc):
-        N, tl, V = logits.shape
-        t = labels32.shape[1]
-        # whole sequences at one stride, rows at another: [N, t + 1, V] is walked in place, its last position skipped
-        if logits.stride(2) != 1 or logits.stride(1) < V or logits.stride(0) < t * logits.stride(1):
-            logits = logits.contiguous()
+        N, t = logits.shape[0], labels32.shape[1]
+        logits, src = _seq_rows(logits, t)
         rows, dev = N * t, logits.device
         stats = torch.empty(3, rows, device=dev, dtype=torch.float32)   # max, log sum exp(x - max), logp
         totals = torch.empty(2, device=dev, dtype=torch.float64)        # sum adv logp, n_live
         loss = torch.empty((), device=dev, dtype=torch.float32)
         seq_logp = torch.empty(N, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.call("care_reward_loss_fwd", _lib.ptr(logits), logits.stride(1), logits.stride(0), t, V, _lib.ptr(labels32),
-                      _lib.ptr(adv), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(stats[2]), _lib.ptr(totals), _lib.ptr(loss),
-                      _lib.ptr(seq_logp), _lib.ptr(acc), rows, tag="reward_loss_fwd")
+            _lib.call("care_reward_loss_fwd", *src, _lib.ptr(labels32), _lib.ptr(adv), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+                      _lib.ptr(stats[2]), _lib.ptr(totals), _lib.ptr(loss), _lib.ptr(seq_logp), _lib.ptr(acc), rows,
+                      tag="reward_loss_fwd")
         ctx.save_for_backward(logits, labels32, adv, stats, totals)
         ctx.mark_non_differentiable(seq_logp, totals)
         return loss, seq_logp, totals
@@ -246,14 +243,12 @@ class _WeightedLogLik(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _gs, _gt):
         logits, labels32, adv, stats, totals = ctx.saved_tensors
-        N, tl, V = logits.shape
         t = labels32.shape[1]
         g = g.to(torch.float32).reshape(1).contiguous()   # a device scalar: the kernel reads it, the host never does
-        d = torch.empty(N, tl, V, device=logits.device, dtype=torch.float32)
+        d, src, dst = _seq_rows_grad(logits, t)
         with torch.cuda.device(logits.device):
-            _lib.call("care_reward_loss_bwd", _lib.ptr(logits), logits.stride(1), logits.stride(0), t, V, _lib.ptr(labels32),
-                      _lib.ptr(adv), _lib.ptr(stats[0]), _lib.ptr(stats[1]), _lib.ptr(totals), _lib.ptr(g), _lib.ptr(d), V, tl * V,
-                      tl, N * t, tag="reward_loss_bwd")
+            _lib.call("care_reward_loss_bwd", *src, _lib.ptr(labels32), _lib.ptr(adv), _lib.ptr(stats[0]),
+                      _lib.ptr(stats[1]), _lib.ptr(totals), _lib.ptr(g), *dst, tag="reward_loss_bwd")
         return d, None, None, None
 
 

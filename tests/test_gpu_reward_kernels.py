@@ -4,7 +4,8 @@ care_cider_score against tests/cider_reference.py (float64, plain Python) within
 and rounds once to fp32, scores are at most 10, half an fp32 ulp at 10 is 4.8e-7 and the bar is four times that.
 care_reward_advantage against the BITS of the same fp32 expression in torch.  care_reward_loss_fwd / _bwd under `_check`'s
 yardstick rule of tests/test_gpu_backward_kernels.py: error against float64 at most FACTOR x the error of torch's own fp32
-evaluation of the same formula + FLOOR x scale.  Every output lies in a guarded buffer between canaries.
+evaluation of the same formula + FLOOR x scale.  Every output lies in a guarded buffer between canaries.  The forward shares
+its row sweeps with care_lang_loss_fwd (csrc/vocab_row.h): the two write the same BITS of rmax, lsum and logp.
 
 Measured on one MI355X: care_cider_score's worst deviation from float64 1.5e-7 / 6.8e-8 / 4.8e-7 on the corpora of 2 / 3 / 40
 videos (bar 2e-6; scores up to 9.6); care_reward_loss_fwd / _bwd worst error / yardstick 2.54 (V 130, 7 x 29, dlogits) and worst
@@ -431,6 +432,51 @@ def test_reward_loss_with_unit_advantages_is_the_language_loss():
     _check(worst, "care_lang_loss_fwd", lang, ref_loss, yard_loss)
     print("weighted", float(ours), "language", float(lang), "float64", float(ref_loss))
     worst.report()
+
+
+@pytest.mark.parametrize("V", [3, 5, 130, 4100, 12290, 16390])
+def test_reward_and_language_forward_share_one_row_sweep(V):
+    """care_reward_loss_fwd and care_lang_loss_fwd (eps = 0) on one buffer and one set of labels write the same BITS of rmax,
+    lsum and logp: both run the sweeps of csrc/vocab_row.h - one order of every sum in every register form, and the maximum as
+    a value does not depend on how ties are ordered.  V = 3 and 5 have head >= V or no float4 at some phases, 4100 puts the
+    two entry points on different register forms (8 float4s a lane against 12), 12290 gives 16 against re-reading, 16390
+    re-reading in both; ld = V .. V + 3 starts consecutive rows at all four 4-byte phases.  One row has a spread of 1e4,
+    the labels have PAD tails, the dropped last position and the padding of a row are NaN."""
+    from care_amd import _lib
+
+    S, P = 2, 3
+    rows = S * P
+    logits, labels, adv = _loss_case(V, S, P, key=5)
+    live = (labels > 0).view(-1)
+    assert 0 < int(live.sum()) < rows, "live rows and PAD tails"
+    lab = labels.to(torch.int32).to(DEV).contiguous()
+    a = adv.to(DEV)
+    phases = set()
+    for ld in range(V, V + 4):
+        buf = torch.full((S, P + 1, ld), float("nan"), device=DEV)
+        buf[:, :P, :V] = logits[:, :P].to(DEV)
+        phases |= {(buf.data_ptr() // 4 + (s * (P + 1) + p) * ld) % 4 for s in range(S) for p in range(P)}
+        rw = {k: _guarded(rows) for k in ("rmax", "lsum", "logp", "seq", "loss")}
+        lg = {k: _guarded(rows) for k in ("lse", "rmax", "lsum", "logp", "row_loss")}
+        w_tot, totals = _guarded(2, torch.float64)
+        pred, sums = torch.empty(rows, dtype=torch.int32, device=DEV), torch.empty(2, device=DEV)
+        counts = torch.empty(3, dtype=torch.int32, device=DEV)
+        _lib.call("care_reward_loss_fwd", buf.data_ptr(), ld, (P + 1) * ld, P, V, lab.data_ptr(), a.data_ptr(), rw["rmax"][1].data_ptr(),
+                  rw["lsum"][1].data_ptr(), rw["logp"][1].data_ptr(), totals.data_ptr(), rw["loss"][1].data_ptr(),
+                  rw["seq"][1].data_ptr(), None, rows)
+        _lib.call("care_lang_loss_fwd", buf.data_ptr(), ld, (P + 1) * ld, P, V, lab.data_ptr(), 0.0, lg["lse"][1].data_ptr(),
+                  lg["rmax"][1].data_ptr(), lg["lsum"][1].data_ptr(), lg["logp"][1].data_ptr(), pred.data_ptr(),
+                  lg["row_loss"][1].data_ptr(), sums.data_ptr(), counts.data_ptr(), None, rows)
+        torch.cuda.synchronize()
+        for k in ("rmax", "lsum", "logp"):
+            assert _intact(rw[k][0], rows) and _intact(lg[k][0], rows), (ld, k)
+            ours, theirs = rw[k][1].cpu(), lg[k][1].cpu()
+            print("V", V, "ld", ld, k, "differing rows", int((ours.view(torch.int32) != theirs.view(torch.int32)).sum()), "of", rows)
+            assert ours.numpy().tobytes() == theirs.numpy().tobytes(), (ld, k, ours.tolist(), theirs.tolist())
+        got = rw["rmax"][1].cpu()
+        assert bool((got[live] == logits[:, :P].reshape(rows, V)[live].max(dim=1).values).all()), "the maximum of a row is exact"
+        assert bool((got[~live] == 0).all()) and bool(torch.isfinite(rw["logp"][1]).all())
+    assert phases == {0, 1, 2, 3}
 
 
 def test_self_critical_loss_under_autograd_without_a_synchronisation():
