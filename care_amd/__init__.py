@@ -12,6 +12,8 @@ and the `r` modality retrieved on device from a bank of caption embeddings (pret
     from care_amd import CaptionBank, attach_retrieval
 and self-critical sequence training on the CIDEr-D of sampled captions (care_amd/reward.py, care_amd/scst.py):
     from care_amd import CiderBank, self_critical_loss, SelfCriticalStep
+and the validation epoch scored on device - corpus BLEU, ROUGE-L and CIDEr over token ids (care_amd/capmetrics.py, care_amd/validation.py):
+    from care_amd import MetricBank, ValidationEpoch
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
@@ -21,7 +23,9 @@ from .interplay import InterplayStep, distillation_mse, ema_update  # noqa: F401
 from .retrieval import CaptionBank, attach_retrieval  # noqa: F401
 from .reward import CiderBank, self_critical_loss  # noqa: F401
 from .scst import SelfCriticalStep  # noqa: F401
+from .capmetrics import MetricBank  # noqa: F401
+from .validation import ValidationEpoch  # noqa: F401
 
-__all__ = ["CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+__all__ = ["MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
            "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
            "CaptionBank", "attach_retrieval"]

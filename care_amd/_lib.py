@@ -125,6 +125,9 @@ SIGNATURES = {
     "care_reward_advantage": [_P, _P, _I, _I, _P, _P, _P],
     "care_reward_loss_fwd": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "care_reward_loss_bwd": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
+    "care_caption_stats": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "care_caption_totals": [_P, _P, _P, _I, _P, _P, _P],
+    "care_beam_winner": [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
 }
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
@@ -173,6 +176,12 @@ class CiderBankDesc(ctypes.Structure):
     _fields_ = [("corpus_keys", c_void_p), ("corpus_lndf", c_void_p), ("n_corpus", c_int64), ("ref_keys", c_void_p),
                 ("ref_w", c_void_p), ("ref_start", c_void_p), ("ref_norm", c_void_p), ("ref_len", c_void_p),
                 ("vid_start", c_void_p), ("n_videos", ctypes.c_int32), ("n_refs", ctypes.c_int32), ("ln_n", ctypes.c_double)]
+
+
+class MetricBankDesc(ctypes.Structure):
+    """care_metric_bank (include/care_hip.h)."""
+    _fields_ = [("cider", CiderBankDesc), ("clip_keys", c_void_p), ("clip_max", c_void_p), ("clip_start", c_void_p),
+                ("ref_tok", c_void_p), ("ref_tok_start", c_void_p)]
 
 
 _libs = {}

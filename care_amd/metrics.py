@@ -4,7 +4,8 @@
   (misc/Crit/crit_lang.py:75-103), from the fused device scoring (engine.score_teacher_forced).
 * `concept_metrics`: F1@k and mAP of the concept probabilities against multi-hot labels
   (misc/Crit/crit_attribute.py:58-89), evaluated on the (all-gathered) `preds_attr`.
-COCO text metrics (BLEU/METEOR/ROUGE/CIDEr) need the reference's Java tools and stay external.
+Of the COCO text metrics only METEOR and the PTB tokenizer need the reference's Java tools and stay external; BLEU, ROUGE-L and
+CIDEr are scored on the device over token ids (care_amd/capmetrics.py, care_amd/validation.py).
 """
 import math
 from typing import Dict

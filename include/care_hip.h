@@ -1059,6 +1059,64 @@ int care_reward_loss_bwd(const float* logits, int64_t ld, int64_t seq_stride, in
                          const float* adv, const float* rmax, const float* lsum, const double* totals, const float* g,
                          float* dlogits, int64_t ldd, int64_t dseq_stride, int seq_rows, int rows, void* stream);
 
+/*
+ * Validation metrics (care_amd/capmetrics.py, care_amd/validation.py; csrc/capmetrics.hip): what the reference's validation
+ * epoch reports besides METEOR (models/Wrapper.py:214-273, misc/cocoeval.py) - corpus BLEU-1..4, ROUGE-L and CIDEr - over
+ * integer token ids, from sufficient statistics that stay on the device for a whole epoch.  The definitions are coco-caption's,
+ * restated in float64 in tests/capmetrics_reference.py.  int / fp32 / double arithmetic in both libraries, no floating-point
+ * atomics, nothing synchronises.
+ *
+ * care_caption_stats: per candidate r - the caption of care_cider_score: tokens[r * ld + col0 .. + min(length[r], width)) with
+ *   ONE trailing `eos` dropped unless with_eos != 0, L tokens - against the references of video[r]:
+ *     rec [r, 12] (int32) = (valid, testlen = L, reflen, guess_1..4, correct_1..4, 0) with
+ *       guess_n   = max(0, L - n + 1),
+ *       correct_n = sum over the caption's distinct n-grams g of min(count in the caption, max over the references of count),
+ *       reflen    = the reference length closest to L, the smaller one of two equally close (min of (|l - L|, l));
+ *     rouge [r] (double) = (1 + b^2) P R / (R + b^2 P) with b = 1.2, P = max_ref lcs / L, R = max_ref (lcs / len(ref)) - the two
+ *       maxima independent of each other - and 0 unless both are non-zero; a reference without tokens has lcs 0 and adds to
+ *       neither.
+ *   The bank (a HOST struct of DEVICE arrays, built once by care_amd.capmetrics.MetricBank) embeds the care_cider_bank of the
+ *   same references (vid_start / n_videos are read from it) and adds
+ *     clip_start [n_videos + 1]: video v owns clip_keys / clip_max [clip_start[v], clip_start[v + 1]) - the unique n-gram keys
+ *     (n = 1..4, the keys of care_cider_score) of its references ascending and each one's largest count in ONE reference;
+ *     ref_tok_start [n_refs + 1]: reference i owns the tokens ref_tok [ref_tok_start[i], ref_tok_start[i + 1]) (after the EOS
+ *     rule, any length).
+ *   One workgroup of 256 per candidate: keys and counts in LDS, the clip table by binary search, integer sums; the references
+ *   dealt to the four waves round-robin, the LCS of a reference by the bit-parallel recurrence on one 64-bit word (lane j holds
+ *   candidate token j; per reference token t: M = ballot(cand == t), U = V & M, V = (V + U) | (V & ~M), V = ~0 at the start;
+ *   lcs = the zero bits among the low L).  A row's bits do not depend on `rows` or on the row's place.
+ *   L == 0 after the EOS rule is an empty caption: valid = 1, the counts 0, reflen the shortest reference, rouge 0.  length[r]
+ *   <= 0, a video[r] outside [0, n_videos) (never dereferenced) or a video without references: an INVALID row, all 12 ints
+ *   and rouge 0.
+ *   NULL tokens / length / video / rec / rouge / bank or a NULL array of the five (or vid_start), rows < 0, width < 1,
+ *   width > 64, col0 < 0, ld < col0 + width, n_videos < 1 -> CARE_EINVAL; clip_keys, clip_start, ref_tok_start or rouge not
+ *   8-byte aligned -> CARE_EALIGN; before anything is launched.  rows == 0 is a no-op that returns 0.
+ * care_caption_totals: ADDS a batch to the running totals  totals_i [12] (int64) = (n_valid, n_invalid, testlen, reflen,
+ *   guess_1..4, correct_1..4),  totals_d [2] (double) = (sum rouge, sum cider); cider (optional, fp32 [rows]) is
+ *   care_cider_score's output.  Invalid rows count in n_invalid and add nothing else.  One workgroup of 1024 in ONE order: a
+ *   thread's rows t, t + 1024, .., a scan in lane order, the waves in wave order.  The integers are exact for any split of an
+ *   epoch into batches; the two doubles depend on the split in their last bits.  The caller zeroes the totals once.
+ *   NULL rec / rouge / totals, rows < 0 -> CARE_EINVAL; rouge / totals not 8-byte aligned -> CARE_EALIGN; rows == 0: a no-op.
+ * care_beam_winner: the caption Translator.translate_batch returns first for each clip of a beam result block (nfin [B],
+ *   fscore / flen [B, cap], fhyp [B, cap, w]): the arg-max of (double)fscore / len_pow[clamp(flen, 0, n_pow - 1)] over the
+ *   first min(nfin, cap) hypotheses, the earliest among equals (a stable sort).  len_pow [n_pow] (double) is the host's table of
+ *   length ** beam_alpha: the division is IEEE's, no pow on the device, so the choice is the host's.  tokens [B, w] = the
+ *   winner's tokens, 0 behind its length; length [B] = its length, 0 (and a row of zeros) when nfin <= 0.
+ *   NULL pointers, B < 0, cap < 1, cap > 64, w < 1, n_pow < 1 -> CARE_EINVAL; len_pow not 8-byte aligned -> CARE_EALIGN;
+ *   B == 0: a no-op.
+ */
+typedef struct care_metric_bank {
+  care_cider_bank cider;
+  const uint64_t* clip_keys; const int32_t* clip_max; const int64_t* clip_start;
+  const int32_t* ref_tok; const int64_t* ref_tok_start;
+} care_metric_bank;
+int care_caption_stats(const int32_t* tokens, int ld, int col0, int width, const int32_t* length, const int32_t* video,
+                       int rows, int with_eos, int eos, const care_metric_bank* bank, int32_t* rec, double* rouge, void* stream);
+int care_caption_totals(const int32_t* rec, const double* rouge, const float* cider, int rows, int64_t* totals_i,
+                        double* totals_d, void* stream);
+int care_beam_winner(const int32_t* nfin, const float* fscore, const int32_t* flen, const int32_t* fhyp, int B, int cap, int w,
+                     const double* len_pow, int n_pow, int32_t* tokens, int32_t* length, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
