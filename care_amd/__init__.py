@@ -14,6 +14,8 @@ and self-critical sequence training on the CIDEr-D of sampled captions (care_amd
     from care_amd import CiderBank, self_critical_loss, SelfCriticalStep
 and the validation epoch scored on device - corpus BLEU, ROUGE-L and CIDEr over token ids (care_amd/capmetrics.py, care_amd/validation.py):
     from care_amd import MetricBank, ValidationEpoch
+and the data set resident in HBM, every training / validation batch built on the device (care_amd/clipstore.py):
+    from care_amd import ClipStore
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
@@ -25,7 +27,8 @@ from .reward import CiderBank, self_critical_loss  # noqa: F401
 from .scst import SelfCriticalStep  # noqa: F401
 from .capmetrics import MetricBank  # noqa: F401
 from .validation import ValidationEpoch  # noqa: F401
+from .clipstore import ClipStore  # noqa: F401
 
-__all__ = ["MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+__all__ = ["ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
            "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
            "CaptionBank", "attach_retrieval"]

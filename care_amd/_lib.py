@@ -128,7 +128,13 @@ SIGNATURES = {
     "care_caption_stats": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "care_caption_totals": [_P, _P, _P, _I, _P, _P, _P],
     "care_beam_winner": [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "care_batch_frame_ids": [_P, _I, _I, _I, _I, _P, _U, _U, _P, _P],
+    "care_batch_gather": [_P, _I, _P, _P, _I, _I, _I, _P],
+    "care_batch_text": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
 }
+FRAMES_EQUAL, FRAMES_SEGMENT, FRAMES_ALL = 0, 1, 2
+FRAME_TYPES = {"equally_sampling": FRAMES_EQUAL, "segment_random": FRAMES_SEGMENT, "all_random": FRAMES_ALL}
+BATCH_MAX_FRAMES, BATCH_MAX_TABLES, BATCH_MAX_ATTR = 128, 8, 3000
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
          "care_argmax_parts_bf16": (c_int, [c_int, c_int]),
@@ -182,6 +188,12 @@ class MetricBankDesc(ctypes.Structure):
     """care_metric_bank (include/care_hip.h)."""
     _fields_ = [("cider", CiderBankDesc), ("clip_keys", c_void_p), ("clip_max", c_void_p), ("clip_start", c_void_p),
                 ("ref_tok", c_void_p), ("ref_tok_start", c_void_p)]
+
+
+class BatchTable(ctypes.Structure):
+    """care_batch_table (include/care_hip.h)."""
+    _fields_ = [("table", c_void_p), ("out", c_void_p), ("pitch", c_int64), ("n_total", ctypes.c_int32),
+                ("row_bytes", ctypes.c_int32), ("n_out", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 _libs = {}

@@ -1117,6 +1117,83 @@ int care_caption_totals(const int32_t* rec, const double* rouge, const float* ci
 int care_beam_winner(const int32_t* nfin, const float* fscore, const int32_t* flen, const int32_t* fhyp, int B, int cap, int w,
                      const double* len_pow, int n_pow, int32_t* tokens, int32_t* length, void* stream);
 
+/*
+ * Training and validation batches built on the device (care_amd/clipstore.py; csrc/batch.hip): the per-video feature tables
+ * and the caption table stay in HBM, a batch is three launches over a list of item indices.  Replaces the reference's
+ * Dataset.__getitem__ + default_collate + H2D copy (dataloader.py:142-190, :232-262, :352-384, :777-814).  Integer and byte
+ * arithmetic only: the same in both library variants; nothing synchronises; plain vector stores throughout.
+ *
+ * The counter-based generator is csrc/sample.hip's mix:  h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin = the splitmix64
+ * finaliser, all in uint64 with wrap-around.  Item key k1 = h(h(seed, epoch), item), `item` = items[b] - the item's index in
+ * the store's infoset, NOT its place b in the batch: an item gets the same frames in whatever batch it lies.
+ *
+ * care_batch_frame_ids (dataloader.py:23-31 get_frame_ids): frame_ids int32 [B, n_frames], ascending per item.  `bounds` is a
+ *   HOST array of n_frames + 1 snippet bounds, int(np.linspace(0, n_total, n_frames + 1)[i]) as the reference computes them
+ *   (misc/utils.py:313); it travels in the kernel arguments.
+ *     CARE_FRAMES_EQUAL   (misc/utils.py:311-317): id_i = (bounds[i] + bounds[i + 1]) / 2 - items, seed, epoch are not read;
+ *     CARE_FRAMES_SEGMENT (:320-326): id_i = bounds[i] + mulhi32((uint32)(h(k1, i) >> 32), bounds[i + 1] - bounds[i]) with
+ *       mulhi32(a, w) = (uint64 a w) >> 32 - uniform over the snippet up to 2^-32, integers only;
+ *     CARE_FRAMES_ALL     (:329-332, a sorted random.sample): frame f has the key h(k1, f); the n_frames frames with the
+ *       smallest (key, f) are chosen and written in ascending f.  One wave per item, the frame on the lane: rank = the number
+ *       of smaller (key, f), a ballot of rank < n_frames, a prefix popcount for the slot.  n_total <= 64 or CARE_ESHAPE.
+ *   The reference draws from Python's / numpy's global generators: its streams cannot be reproduced, the distribution and
+ *   every deterministic rule are.
+ *   NULL frame_ids / bounds (items: for the two random types), B < 0, n_total < 1, n_frames < 1, bounds that do not start at 0,
+ *   end at n_total and ascend -> CARE_EINVAL; an unknown type -> CARE_EDTYPE; n_frames > CARE_BATCH_MAX_FRAMES, or for the two
+ *   random types n_frames > n_total (an empty snippet: the reference's randint / sample raise) -> CARE_ESHAPE; a pointer that
+ *   is not 4-byte aligned -> CARE_EALIGN; all before anything is launched.  B == 0 is a no-op that returns 0.
+ *
+ * care_batch_gather (dataloader.py:232-262 _load_feats with load_feats_type 0, :808-814 load_r_feats, default_collate):
+ *   every modality of the batch in ONE launch.  care_batch_table (a HOST array, `count` <= CARE_BATCH_MAX_TABLES of them, in
+ *   the kernel arguments): table [n_videos, n_total, pitch bytes] - `pitch` a multiple of 16, >= row_bytes, the table 16-byte
+ *   aligned, so every source row is; out [B, n_out, row_bytes] dense.  Row (b, j) of a table is row_bytes BYTES copied from
+ *   source row (video_ids[b], n_total == 1 ? 0 : frame_ids[b * n_frames + j]): n_total == 1 is a per-video vector that every
+ *   frame id reads (dataloader.py:247-251) - or, with n_out == 1, one whole block per video such as the first retrieval_topk
+ *   rows of `r`; n_total > 1 needs n_out == n_frames.  A video id outside [0, n_videos) or a frame id outside [0, n_total)
+ *   is never dereferenced: the row is zeros.  row_bytes a multiple of 16 and out 16-byte aligned: 16-byte loads and stores;
+ *   else a multiple of 4 and out 4-byte aligned: 16-byte loads, 4-byte stores; else (a multiple of 2) 2-byte stores - never
+ *   a byte at or beyond row_bytes of a destination row.  The source is read once an epoch (non-temporal loads), the
+ *   destination is read next by the embedder (plain stores).
+ *   NULL pointers (frame_ids: only when a table has n_total > 1), count < 1, B < 0, n_videos < 1, n_frames < 1, n_total < 1,
+ *   n_out < 1, row_bytes < 2 or odd, pitch < row_bytes -> CARE_EINVAL; count > CARE_BATCH_MAX_TABLES, n_total > 1 with
+ *   n_out != n_frames, more than 2^31 - 1 KiB-pieces of rows in one table's output -> CARE_ESHAPE; a table or pitch that is not 16-byte aligned, an out that is not 2-byte aligned, an id
+ *   array that is not 4-byte aligned -> CARE_EALIGN; all before anything is launched.  B == 0: a no-op.
+ *
+ * care_batch_text (dataloader.py:352-384 _getitem_text_only, :524-571 _prepare_input_ids / _make_source_target, :661-675
+ *   _padding; misc/utils_corpora.py:424-441 get_vid2attribute_mappings): one workgroup per item.  The caption table: tokens
+ *   int32 flat, cap_start int32 [n_caps + 1] (caption c owns tokens [cap_start[c], cap_start[c + 1])), cap_video int32
+ *   [n_caps], vid_first int32 [n_videos + 1] (video v owns the captions [vid_first[v], vid_first[v + 1])).  item_cap int32
+ *   [n_items]: the caption of infoset item i; c = item_cap[items[b]], v = cap_video[c].  Written:
+ *     video_ids [b] = v, caption_ids [b] = c - vid_first[v] (the reference's cap_id), both int32;
+ *     with P = the caption cut to max_len, its last place EOS when it was longer, PAD behind a shorter one:
+ *     input_ids [b, 0 .. max_len - 2] = P[0 ..], labels [b, 0 .. max_len - 2] = P[1 ..], both int64;
+ *     labels_attr [b, a] fp32 (optional, with n_attributes) = 1.0 when a token attribute_start + a stands in ANY caption of v,
+ *     its first and last token (BOS, EOS) apart, else 0.0 - a bitmap in LDS set by atomic or, then read out.
+ *   An items[b] outside [0, n_items) is never dereferenced: video_ids = caption_ids = -1, PAD rows and zeros.
+ *   NULL pointers (labels_attr apart), B < 0, n_items < 1, n_caps < 1, n_videos < 1, max_len < 2 -> CARE_EINVAL; labels_attr
+ *   with n_attributes outside [1, CARE_BATCH_MAX_ATTR] -> CARE_ESHAPE; input_ids / labels not 8-byte, another array not
+ *   4-byte aligned -> CARE_EALIGN; all before anything is launched.  B == 0: a no-op.
+ */
+#define CARE_FRAMES_EQUAL 0
+#define CARE_FRAMES_SEGMENT 1
+#define CARE_FRAMES_ALL 2
+#define CARE_BATCH_MAX_FRAMES 128
+#define CARE_BATCH_MAX_TABLES 8
+#define CARE_BATCH_MAX_ATTR 3000
+typedef struct care_batch_table {
+  const void* table; void* out;
+  int64_t pitch;
+  int32_t n_total; int32_t row_bytes; int32_t n_out; int32_t reserved;
+} care_batch_table;
+int care_batch_frame_ids(const int32_t* items, int B, int n_total, int n_frames, int random_type, const int32_t* bounds,
+                         uint64_t seed, uint64_t epoch, int32_t* frame_ids, void* stream);
+int care_batch_gather(const care_batch_table* tables, int count, const int32_t* video_ids, const int32_t* frame_ids,
+                      int n_videos, int B, int n_frames, void* stream);
+int care_batch_text(const int32_t* items, int B, const int32_t* item_cap, int n_items, const int32_t* tokens,
+                    const int32_t* cap_start, const int32_t* cap_video, const int32_t* vid_first, int n_caps, int n_videos,
+                    int max_len, int pad, int eos, int attribute_start, int n_attributes, int32_t* video_ids,
+                    int32_t* caption_ids, int64_t* input_ids, int64_t* labels, float* labels_attr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
