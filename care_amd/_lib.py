@@ -128,6 +128,7 @@ SIGNATURES = {
     "care_caption_stats": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "care_caption_totals": [_P, _P, _P, _I, _P, _P, _P],
     "care_beam_winner": [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "care_concept_metrics": [_P, _L, _P, _L, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "care_batch_frame_ids": [_P, _I, _I, _I, _I, _P, _U, _U, _P, _P],
     "care_batch_gather": [_P, _I, _P, _P, _I, _I, _I, _P],
     "care_batch_text": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
@@ -135,6 +136,7 @@ SIGNATURES = {
 FRAMES_EQUAL, FRAMES_SEGMENT, FRAMES_ALL = 0, 1, 2
 FRAME_TYPES = {"equally_sampling": FRAMES_EQUAL, "segment_random": FRAMES_SEGMENT, "all_random": FRAMES_ALL}
 BATCH_MAX_FRAMES, BATCH_MAX_TABLES, BATCH_MAX_ATTR = 128, 8, 3000
+CONCEPT_MAX_K, CONCEPT_MAX_TOPK = 4096, 8
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
          "care_argmax_parts_bf16": (c_int, [c_int, c_int]),

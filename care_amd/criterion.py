@@ -18,7 +18,8 @@
   counted before their copy, so `get_loss` stays free of host synchronisation; for labels already on the device the count
   of live rows - 4 bytes - is read back: the one exception.
 * `NoisyOrMIL` (crit_attribute.py): BCE of the clamped concept probabilities over the number of positives, F1@k, mAP -
-  care_noisy_or_bce_fwd / _bwd; F1@k / mAP with care_amd/metrics.py's formulas.
+  care_noisy_or_bce_fwd / _bwd; F1@k / mAP by care_concept_metrics (csrc/concept_metrics.hip) into the recorder's device
+  doubles: no sort, no top-k, nothing kept between steps; equal probabilities rank by column.
 * `Criterion` (base.py:50-113): scales, sums and records them.
 
 Both losses are torch.autograd.Functions, so `loss.backward()` feeds training.py's `_Linear.backward` of the vocabulary head
@@ -40,7 +41,7 @@ import torch
 
 from ._lib import call, ptr
 from .constants import PAD
-from .metrics import TOPK_LIST
+from .metrics import TOPK_LIST, concept_metrics_device
 
 __all__ = ["get_criterion", "Criterion", "CritBase", "LanguageGeneration", "NoisyOrMIL", "DeferredLogits", "head_chunks"]
 
@@ -408,7 +409,7 @@ class NoisyOrMIL(CritBase):
         super().__init__(keys=["preds_attr", "avg_prob_attr", "labels_attr"] if keys is None else keys, batch_mean=True)
         self.topk_list = list(TOPK_LIST)
         self.calculate_mAP = opt.get("calculate_mAP", False)
-        self.acc = None
+        self.acc = self.acc_clips = None
 
     def _step(self, index_indicator, preds_attr, avg_prob_attr, labels_attr, *others):
         assert not len(others)
@@ -416,57 +417,32 @@ class NoisyOrMIL(CritBase):
         preds = _rows_f32(preds_attr)
         labels = _rows_f32(labels_attr.to(preds.device))      # [B, Kl >= K]: the kernels use the first K columns in place
         B, K = preds.shape
-        if self.acc is None:
-            self.acc = torch.zeros(1 + len(self.topk_list), device=preds.device, dtype=torch.float64)
+        if self.acc is None:   # the loss, sum F1@k for each k, sum AP; beside them the kernel's (clips, clips without a positive)
+            self.acc = torch.zeros(2 + len(self.topk_list), device=preds.device, dtype=torch.float64)
+            self.acc_clips = torch.zeros(2, device=preds.device, dtype=torch.int64)
         loss = _NoisyOrBCE.apply(preds, labels, self.acc)
         if hasattr(self, "f1_count"):   # (as in the reference: metrics only once reset_recorder() has been called)
-            with torch.no_grad():
-                p = torch.clamp(preds.detach(), 0.01, 0.99)
-                y = labels[:, :K]
-                _, cand = p.topk(max(self.topk_list), dim=1, sorted=True, largest=True)
-                n_pos = y.sum(1)
-                f1s = []
-                for k in self.topk_list:   # metrics.concept_metrics' formulas, summed on the device
-                    hit = y.gather(1, cand[:, :k]).sum(1)
-                    hit = torch.where(hit.eq(0), torch.full_like(hit, 1e-3), hit)
-                    precision, recall = hit / k, hit / n_pos
-                    f1s.append((2 * precision * recall / (precision + recall)).sum())
-                self.acc[1:] += torch.stack(f1s).double()
-                self.f1_count += B
-                if self.calculate_mAP:
-                    self.ap_pending.append((p, y))
+            # F1@k and AP of every clip and their sums in ONE call (csrc/concept_metrics.hip): acc[1:] = sum F1@k .., sum AP
+            concept_metrics_device(preds, labels, self.topk_list, totals=(self.acc[1:], self.acc_clips))
+            self.f1_count += B
         return loss
 
     def get_fieldsnames(self, prefix=""):
-        return ["%sF1-%02d" % (prefix, item) for item in self.topk_list] + (["%smAP" % prefix] if hasattr(self, "ap_pending") else [])
-
-    def _mean_ap(self) -> float:
-        """crit_attribute.py:72-86 over the batches since the reset (the row loop runs here, not inside the step)."""
-        aps = []
-        for p, y in self.ap_pending:
-            _, idx = p.sort(dim=1, descending=True)
-            _, rank = idx.sort(dim=1)
-            rank, y = rank.cpu(), y.cpu()
-            for i in range(y.shape[0]):
-                pos = y[i].nonzero().squeeze(1)
-                hit_rank, _ = rank[i][pos].sort()
-                ids = torch.arange(len(pos))
-                aps.append(float(((ids + 1).float() / (hit_rank + 1)).mean()))
-        return sum(aps) / len(aps) if aps else 0
+        return ["%sF1-%02d" % (prefix, item) for item in self.topk_list] + (["%smAP" % prefix] if getattr(self, "ap_on", False) else [])
 
     def get_info(self, state=None):
         if not hasattr(self, "f1_count"):
             raise AttributeError("NoisyOrMIL.get_info() before reset_recorder()")
         if state is None and self.acc is not None:
             state = self.acc.cpu().tolist()
-        f1 = [s / self.f1_count for s in state[1:]] if (state is not None and self.f1_count) else [0] * len(self.topk_list)
-        return self.get_fieldsnames(), f1 + ([self._mean_ap()] if hasattr(self, "ap_pending") else [])
+        n = len(self.topk_list)
+        avg = [s / self.f1_count for s in state[1:]] if (state is not None and self.f1_count) else [0] * (n + 1)
+        return self.get_fieldsnames(), avg[:n] + ([avg[n]] if self.ap_on else [])
 
     def reset_recorder(self):
-        self.acc = None
+        self.acc = self.acc_clips = None
         self.f1_count = 0
-        if self.calculate_mAP:
-            self.ap_pending = []
+        self.ap_on = bool(self.calculate_mAP)
 
 
 class Criterion(object):

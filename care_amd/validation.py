@@ -12,6 +12,13 @@ The validation-side counterpart of SelfCriticalStep and InterplayStep - what `Wr
 another, so the engine's workspaces are consumed before the next decode overwrites them.  No token, length or score is read on
 the host during the epoch; `run` ends with ONE read of 15 words.
 
+A captioner with a concept head whose batches carry `labels_attr` (ClipStore's validate batches do) is also scored as the
+reference's eval criterion scores it (models/Wrapper.py:182-184, :421: get_criterion(opt, skip_crit_list=['lang'],
+override_opt={'calculate_mAP': True})): the decode's own `preds_attr` - in eval mode the one `feedforward_step` would produce -
+goes through care_concept_metrics and care_noisy_or_bce_fwd into totals of their own beside the state, in the same
+`engine.lock` section; the scores gain `mAP` (Wrapper.py:245-248), `F1-05` .. `F1-50`, `V-Attr Loss` and `n_no_positive`, for
+one more read at the epoch's end.  Without a concept head or without `labels_attr`: nothing new, no launch and no key.
+
 A resident launch that gives up reports non-positive lengths; such rows count as invalid.  If the epoch ends with any, it is
 run once more with the resident decodes switched off (the Translator's own retry, applied to the epoch), and the Translator's
 error is raised if rows are still without a caption.
@@ -23,6 +30,7 @@ import torch
 
 from . import _lib
 from .capmetrics import METRIC_SUM, TOTALS, MetricBank, check_metric_sum
+from .metrics import TOPK_LIST, concept_metrics_device, concept_scores, concept_totals
 from .framework import TransformerSeq2Seq
 from .translator import Translator_ARFormer
 
@@ -51,17 +59,19 @@ class ValidationEpoch(object):
         self.opt, self.captioner, self.bank = opt, captioner, bank
         self.beam_size, self.beam_alpha = int(self.translator.beam_size), self.translator.beam_alpha
         self._len_pow = None
+        self.concept = None   # the concept totals of the last accumulate(): (doubles [n_topk + 1], int64 [2], loss double [1])
         self.last = {}
 
     # ------------------------------------------------------------------ one batch: decode, score, accumulate
     def _decode(self, engine, feats):
-        """(tokens int32 [B, <= 64] without BOS, length int32 [B]) of the caption translate_batch returns first, on the device."""
+        """(tokens int32 [B, <= 64] without BOS, length int32 [B]) of the caption translate_batch returns first, on the device,
+        and the encoder's outputs of the pass."""
         T = engine.T
         if self.beam_size == 1:
-            _, fed, length, _ = engine.translate_greedy(feats, use_graph=False, early_exit=False)
-            return fed[:, 1: T + 1], length
+            enc, fed, length, _ = engine.translate_greedy(feats, use_graph=False, early_exit=False)
+            return fed[:, 1: T + 1], length, enc
         need = max(self.beam_size, int(self.translator.topk))
-        _, nfin, fscore, flen, fhyp = engine.translate_beam(feats, self.beam_size, need, use_graph=False, early_exit=False)
+        enc, nfin, fscore, flen, fhyp = engine.translate_beam(feats, self.beam_size, need, use_graph=False, early_exit=False)
         B, cap, w = fhyp.shape
         if self._len_pow is None or self._len_pow.device != fhyp.device:
             self._len_pow = torch.from_numpy(self.translator._len_pow).to(fhyp.device)
@@ -69,7 +79,25 @@ class ValidationEpoch(object):
         length = torch.empty(B, dtype=torch.int32, device=fhyp.device)
         _lib.call("care_beam_winner", _lib.ptr(nfin), _lib.ptr(fscore), _lib.ptr(flen), _lib.ptr(fhyp), B, cap, w,
                   _lib.ptr(self._len_pow), self._len_pow.numel(), _lib.ptr(tokens), _lib.ptr(length), tag="beam_winner")
-        return tokens, length
+        return tokens, length, enc
+
+    def _score_concepts(self, enc, labels_attr):
+        """F1@k / AP of the batch's `preds_attr` and the eval criterion's BCE (crit_attribute.py:38-48, :58-89) into the
+        epoch's concept totals: three small launches, nothing read."""
+        preds = enc["preds_attr"]
+        labels = labels_attr.to(preds.device)
+        labels = labels if labels.dtype == torch.float32 else labels.float()
+        labels = labels if labels.stride(-1) == 1 else labels.contiguous()
+        B, K = preds.shape
+        if labels.dim() != 2 or labels.shape[0] != B or labels.shape[1] < K:
+            raise ValueError("`labels_attr` {} for concept probabilities {}".format(tuple(labels.shape), (B, K)))
+        if self.concept is None:
+            self.concept = concept_totals(len(TOPK_LIST), preds.device) + (torch.zeros(1, dtype=torch.float64, device=preds.device),)
+        concept_metrics_device(preds, labels, TOPK_LIST, totals=self.concept[:2])
+        rl = torch.empty(2, B, device=preds.device, dtype=torch.float32)
+        sums = torch.empty(1, device=preds.device, dtype=torch.float32)
+        _lib.call("care_noisy_or_bce_fwd", _lib.ptr(preds), preds.stride(0), _lib.ptr(labels), labels.stride(0), _lib.ptr(rl[0]),
+                  _lib.ptr(rl[1]), _lib.ptr(sums), _lib.ptr(self.concept[2]), B, K, tag="concept_bce")
 
     def _pass(self, model, batches, state):
         engine = model.engine()
@@ -89,14 +117,17 @@ class ValidationEpoch(object):
                 video = self.bank.rows(batch["video_ids"])
                 if video.numel() != feats[0].shape[0]:
                     raise ValueError("{} `video_ids` for {} clips".format(video.numel(), feats[0].shape[0]))
-                tokens, length = self._decode(engine, feats)
+                tokens, length, enc = self._decode(engine, feats)
                 self.bank.accumulate(self.bank.score(tokens, length, video), state[:TOTALS])
                 state[TOTALS] += (length <= 0).sum()   # rows a resident launch gave up on (on the device, like the rest)
+                if batch.get("labels_attr") is not None and "preds_attr" in enc:   # a concept head and its labels
+                    self._score_concepts(enc, batch["labels_attr"])
 
     def accumulate(self, batches, resident: bool = True) -> torch.Tensor:
         """Decodes and scores `batches` and returns the epoch's state - int64 [15] on the device: MetricBank's totals and the
         number of rows that came back without a caption - WITHOUT reading anything on the host.  resident False: with the
-        resident decodes switched off.  The model is put into eval mode and comes back as it was."""
+        resident decodes switched off.  The model is put into eval mode and comes back as it was.  The concept totals of the
+        pass (None when nothing was scored) are `self.concept`, zero at the start of every call like the state."""
         if self.bank.desc is None:
             raise RuntimeError("the bank was built with device=None (host tables only): the validation epoch runs on the MI355X")
         model = self.captioner
@@ -110,6 +141,7 @@ class ValidationEpoch(object):
                     engine.resident_max_rows = engine.resident_beam_max_rows = 0
                 try:
                     state = torch.zeros(TOTALS + 1, dtype=torch.int64, device=self.bank.device)
+                    self.concept = None
                     self._pass(model, batches, state)
                 finally:
                     engine.resident_max_rows, engine.resident_beam_max_rows = keep
@@ -118,9 +150,18 @@ class ValidationEpoch(object):
         return state
 
     def scores(self, state: torch.Tensor):
-        """(MetricBank.scores' dict, rows without a caption) of an epoch's state: the ONE host read."""
+        """(MetricBank.scores' dict, rows without a caption) of an epoch's state: the ONE host read - and one more, of 10
+        doubles, when the epoch scored concepts: `mAP`, `F1-05` .. `F1-50`, `V-Attr Loss` (the sum of the clips' BCE over the
+        clip count: base.py:95's batch-mean recorder) and `n_no_positive` (clips whose F1 / AP are NaN) join the scores."""
         host = state.cpu()
-        return self.bank.scores(host[:TOTALS], self.metric_sum), int(host[TOTALS])
+        scores = self.bank.scores(host[:TOTALS], self.metric_sum)
+        if self.concept is not None:
+            d, i, loss = self.concept
+            c = torch.cat([d, loss, i.double()]).cpu().tolist()   # (counts below 2^53: exact as doubles)
+            n = len(TOPK_LIST)
+            scores.update(concept_scores(c[:n + 1], [int(c[n + 2]), int(c[n + 3])], TOPK_LIST))
+            scores["V-Attr Loss"] = c[n + 1] / c[n + 2] if c[n + 2] else 0
+        return scores, int(host[TOTALS])
 
     def run(self, batches) -> dict:
         """The scores of the epoch over `batches` (dicts with `feats` on the device and `video_ids`): MetricBank.scores' dict of

@@ -1118,6 +1118,46 @@ int care_beam_winner(const int32_t* nfin, const float* fscore, const int32_t* fl
                      const double* len_pow, int n_pow, int32_t* tokens, int32_t* length, void* stream);
 
 /*
+ * Concept metrics (care_amd/metrics.py, care_amd/criterion.py, care_amd/validation.py; csrc/concept_metrics.hip): the metric
+ * half of NoisyOrMIL._step (misc/Crit/crit_attribute.py:58-89) - F1@k and average precision of the concept probabilities
+ * against multi-hot labels - without a sort, and their sums over an epoch in totals that stay on the device: what the
+ * reference's eval criterion (models/Wrapper.py:182-184, :421: calculate_mAP) feeds into `mAP` / `best_mAP` (:59-71, :245-248).
+ * int, fp32 compares and double arithmetic in both libraries, no floating-point atomics, nothing synchronises.
+ *
+ * care_concept_metrics: preds fp32 [B, ldp >= K], labels fp32 [B, ldl >= K] read in place (as care_noisy_or_bce_fwd reads
+ *   them); a POSITIVE of clip b is a column j < K with labels[b, j] != 0, P of them.  ONE total order of the columns of a clip:
+ *   by p = clamp(preds, 0.01, 0.99) in fp32 (torch.clamp: NaN stays NaN) descending, NaN before every number (torch's
+ *   descending order); among equal values, or among NaNs, the lower column first (sort(stable=True)).  With
+ *     rank_j = the number of columns i < K before j,  posrank_j = the number of positives before j:
+ *     hits [b, t] (int32 [B, n_topk], optional) = #{positive j : rank_j < topk[t]}       (crit_attribute.py:59-64),
+ *     n_pos [b]   (int32 [B], optional)         = P                                      (:60),
+ *     ap [b]      (double [B], optional)        = (sum over the positives of (posrank_j + 1) / (rank_j + 1)) / P   (:73-84),
+ *   the terms added in ascending posrank - the reference's order - grouped one fixed way; every division and sum in double: the
+ *   operands are integers, so this is the exact value up to its own rounding.  P == 0: ap = 0 / 0 = NaN, from the same
+ *   expression.  topk is a HOST array of n_topk <= CARE_CONCEPT_MAX_TOPK positive ints; it travels in the kernel arguments.
+ *   One workgroup of 256 per clip: keys and a bitmap of the positives in LDS, the positives compacted by ballot and prefix
+ *   count and dealt to the four waves, per positive one sweep of the K columns by 64 lanes that counts both integers.  A
+ *   clip's bits do not depend on B or on the clip's place.  K <= CARE_CONCEPT_MAX_K (the LDS form).
+ *   totals_d (double [n_topk + 1]) / totals_i (int64 [2]), optional but only together: a second launch of ONE workgroup of
+ *   1024 ADDS the batch, in one order (a thread's clips t, t + 1024, .., a scan in lane order, the waves in wave order, as
+ *   care_caption_totals):  totals_d[t] += sum_b F1@topk[t],  totals_d[n_topk] += sum_b ap[b],  totals_i = (clips, clips with
+ *   P == 0), with  hit = hits == 0 ? 1e-3 : hits,  precision = hit / k,  recall = hit / P,  F1 = 2 precision recall /
+ *   (precision + recall)  in double (:65-68); P == 0 makes recall infinite and F1 NaN as in the reference - and the clip is
+ *   counted in totals_i[1], so a caller can tell.  The totals are sums of the per-clip outputs: with totals, ap, n_pos and
+ *   (for n_topk > 0) hits must be given.  The integers are exact for any split of an epoch into batches; the doubles depend
+ *   on the split in their last bits.  The caller zeroes the totals once.
+ *   NULL preds / labels, B < 0, K < 1, n_topk outside [0, CARE_CONCEPT_MAX_TOPK], NULL topk with n_topk > 0, a topk[t] < 1,
+ *   ldp or ldl < K, one of totals_d / totals_i without the other, totals without the per-clip outputs -> CARE_EINVAL;
+ *   K > CARE_CONCEPT_MAX_K, a topk[t] > K (the reference's topk(50) raises there) -> CARE_ESHAPE; ap / totals_d / totals_i not
+ *   8-byte, another array not 4-byte aligned -> CARE_EALIGN; all before anything is launched.  B == 0: a no-op that returns 0.
+ */
+#define CARE_CONCEPT_MAX_K 4096
+#define CARE_CONCEPT_MAX_TOPK 8
+int care_concept_metrics(const float* preds, int64_t ldp, const float* labels, int64_t ldl, int B, int K, const int32_t* topk,
+                         int n_topk, double* ap, int32_t* hits, int32_t* n_pos, double* totals_d, int64_t* totals_i,
+                         void* stream);
+
+/*
  * Training and validation batches built on the device (care_amd/clipstore.py; csrc/batch.hip): the per-video feature tables
  * and the caption table stay in HBM, a batch is three launches over a list of item indices.  Replaces the reference's
  * Dataset.__getitem__ + default_collate + H2D copy (dataloader.py:142-190, :232-262, :352-384, :777-814).  Integer and byte
