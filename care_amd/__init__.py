@@ -16,6 +16,9 @@ and the validation epoch scored on device - corpus BLEU, ROUGE-L and CIDEr over 
     from care_amd import MetricBank, ValidationEpoch
 and the data set resident in HBM, every training / validation batch built on the device (care_amd/clipstore.py):
     from care_amd import ClipStore
+and the test epoch - per-video scores, the predictions and the caption analysis `ave_length` / `novel` / `unique` / `usage`
+against the training captions, all kept on the device (care_amd/corpusstats.py, care_amd/testepoch.py):
+    from care_amd import CorpusBank, EpochCaptions, TestEpoch
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
@@ -28,7 +31,9 @@ from .scst import SelfCriticalStep  # noqa: F401
 from .capmetrics import MetricBank  # noqa: F401
 from .validation import ValidationEpoch  # noqa: F401
 from .clipstore import ClipStore  # noqa: F401
+from .corpusstats import CorpusBank, EpochCaptions  # noqa: F401
+from .testepoch import TestEpoch  # noqa: F401
 
-__all__ = ["ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+__all__ = ["CorpusBank", "EpochCaptions", "TestEpoch", "ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
            "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
            "CaptionBank", "attach_retrieval"]

@@ -128,6 +128,9 @@ SIGNATURES = {
     "care_caption_stats": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "care_caption_totals": [_P, _P, _P, _I, _P, _P, _P],
     "care_beam_winner": [_P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P, _P],
+    "care_corpus_insert": [_P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P, _P, _P],
+    "care_corpus_totals": [_P, _P],
+    "care_caption_model_score": [_P, _P, _P, _I, _I, _P, _I, _P, _P],
     "care_concept_metrics": [_P, _L, _P, _L, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "care_batch_frame_ids": [_P, _I, _I, _I, _I, _P, _U, _U, _P, _P],
     "care_batch_gather": [_P, _I, _P, _P, _I, _I, _I, _P],
@@ -137,6 +140,7 @@ FRAMES_EQUAL, FRAMES_SEGMENT, FRAMES_ALL = 0, 1, 2
 FRAME_TYPES = {"equally_sampling": FRAMES_EQUAL, "segment_random": FRAMES_SEGMENT, "all_random": FRAMES_ALL}
 BATCH_MAX_FRAMES, BATCH_MAX_TABLES, BATCH_MAX_ATTR = 128, 8, 3000
 CONCEPT_MAX_K, CONCEPT_MAX_TOPK = 4096, 8
+CORPUS_MAX_CAPTION, CORPUS_BITMAP_WORDS, CORPUS_TOTALS = 64, 2048, 8
 PLAIN = {"care_version": (c_int, []), "care_arch": (c_char_p, []), "care_source_hash": (c_char_p, []),
          "care_build_flags": (c_char_p, []), "care_h16": (c_char_p, []), "care_argmax_parts": (c_int, [c_int]),
          "care_argmax_parts_bf16": (c_int, [c_int, c_int]),
@@ -190,6 +194,17 @@ class MetricBankDesc(ctypes.Structure):
     """care_metric_bank (include/care_hip.h)."""
     _fields_ = [("cider", CiderBankDesc), ("clip_keys", c_void_p), ("clip_max", c_void_p), ("clip_start", c_void_p),
                 ("ref_tok", c_void_p), ("ref_tok_start", c_void_p)]
+
+
+class CorpusBankDesc(ctypes.Structure):
+    """care_corpus_bank (include/care_hip.h)."""
+    _fields_ = [("keys", c_void_p), ("start", c_void_p), ("tokens", c_void_p), ("n", c_int64), ("key_mask", c_uint64)]
+
+
+class EpochSetDesc(ctypes.Structure):
+    """care_epoch_set (include/care_hip.h)."""
+    _fields_ = [("slots", c_void_p), ("tokens", c_void_p), ("length", c_void_p), ("keys", c_void_p), ("bitmap", c_void_p),
+                ("totals", c_void_p), ("capacity", ctypes.c_int32), ("reserved", ctypes.c_int32), ("key_mask", c_uint64)]
 
 
 class BatchTable(ctypes.Structure):

@@ -1234,6 +1234,81 @@ int care_batch_text(const int32_t* items, int B, const int32_t* item_cap, int n_
                     int max_len, int pad, int eos, int attribute_start, int n_attributes, int32_t* video_ids,
                     int32_t* caption_ids, int64_t* input_ids, int64_t* labels, float* labels_attr, void* stream);
 
+/*
+ * Test epoch (care_amd/corpusstats.py, care_amd/testepoch.py; csrc/corpus_stats.hip): what the reference's test run reports on
+ * top of the corpus scores - Wrapper.test_epoch_end (models/Wrapper.py:75-149): the caption analysis `ave_length`, `novel`,
+ * `unique`, `usage` of analyze_length_novel_unique (misc/utils.py:406-419 over cal_n_gram :390-403 and cal_gt_n_gram :375-387)
+ * and the `score` of a prediction (Wrapper.py:206-210) - as integers and doubles that stay on the device for a whole epoch.
+ * Integer and double arithmetic only: the same in both libraries; ordinary 32- / 64-bit integer atomics, no floating-point
+ * atomics; nothing synchronises.
+ *
+ * A CAPTION is tokens[r * ld + col0 .. + min(max(length[r], 0), width)) (each token & 0xFFFF, as care_caption_stats reads it)
+ * cut at the first `eos` or `pad`: the words to_sentence yields (misc/utils.py:117-137), n <= 64 of them.  Its KEY:
+ *     key = (h(n, 64) + sum_j h(token_j, j)) & key_mask,  h(a, i) = fin(a + 0x9E3779B97F4A7C15 (i + 1)),
+ *   fin the splitmix64 finaliser, all in uint64 with wrap-around (care_amd.corpusstats.caption_key is the same function in
+ *   numpy).  A key only says where to look: equality is always decided token by token, so every count below is exact.
+ * care_corpus_bank (a HOST struct of DEVICE arrays, care_amd.corpusstats.CorpusBank): the DISTINCT training captions -
+ *   cal_gt_n_gram's `gt_sents`, the ids tmp[1:-1] of every training caption - with keys [n] ascending, caption i owning
+ *   tokens [start[i], start[i + 1]) (any length; one of more than 64 tokens equals no caption).  key_mask (all ones by
+ *   default, the same in the bank and in the set) is ANDed onto every key: a small mask makes long runs of equal keys and long
+ *   probe chains out of a handful of captions, for the tests.
+ * care_epoch_set (a HOST struct of DEVICE arrays, care_amd.corpusstats.EpochCaptions): the captions of the epoch so far.
+ *   tokens [capacity, 64] / length [capacity] / keys [capacity]: the epoch store, row g the g-th caption inserted (zeros behind
+ *   its length); slots [capacity]: the open-addressing table, -1 = empty, else the store row of the FIRST caption of its kind;
+ *   bitmap [CARE_CORPUS_BITMAP_WORDS]: bit t set when token t stands in a caption; totals [CARE_CORPUS_TOTALS] (uint64):
+ *     N_CAPTIONS, LENGTH_SUM (an empty caption counts 1: ''.split(' ') is ['']), N_DISTINCT, N_NOVEL (distinct captions no
+ *     training caption equals; the empty caption is novel unless a training caption is empty), N_EMPTY, USAGE (written by
+ *     care_corpus_totals), N_OVERFLOW (captions that found no slot: 0 unless the caller broke the rules below), 0.
+ *   The caller zeroes tokens / bitmap / totals and sets every slot to -1 once an epoch.  `capacity` is a power of two.
+ * care_corpus_insert: ADDS the `rows` captions of a batch as store rows [cursor, cursor + rows).  Two launches behind one
+ *   another, one wave per caption with a token per lane: the first cuts the captions and writes their store rows and keys
+ *   (keys_out [rows], optional, gets the keys too); the second sets the tokens' bits (atomic or), adds to the totals and
+ *   probes the table from slot key & (capacity - 1) onwards with wrap-around: an empty slot is taken by a 32-bit atomicCAS - the
+ *   caption is the first of its kind, and is looked up in the bank (binary search for the first equal key, then along the run
+ *   of equal keys); a slot that names a row with other tokens is passed; one that names an equal row ends the probe - a
+ *   duplicate.  A slot only ever names a row written by an EARLIER launch, so no fence is needed; which of several equal
+ *   captions of one launch wins is a race that no total depends on.  The totals are integers: exact for any split of an epoch
+ *   into batches.  The caller advances `cursor` by `rows` (a host integer); the same cursor twice counts the batch twice.
+ *   NULL tokens / length / bank / set or a NULL array of either struct, rows < 0, cursor < 0, width < 1, col0 < 0,
+ *   ld < col0 + width, bank n < 0, a bank whose key_mask is not the set's -> CARE_EINVAL; a capacity that is not a power of two, width > 64, cursor + rows > capacity
+ *   -> CARE_ESHAPE; a uint64 / int64 array that is not 8-byte aligned -> CARE_EALIGN; all before anything is launched.
+ *   rows == 0: a no-op that returns 0.
+ * care_corpus_totals: totals[USAGE] = the set bits of the bitmap + (N_EMPTY != 0): the `usage` of the epoch so far (len of
+ *   cal_n_gram's gram_count with n = 1, the empty word included).  One workgroup; WRITES, so it may run at any time.
+ * care_caption_model_score: out [B] (double) = the `score` translate_batch returns with a clip's first caption: the value
+ *   (double)fscore / len_pow[clamp(flen, 0, n_pow - 1)] of care_beam_winner's choice among the first min(nfin, cap)
+ *   hypotheses of fscore / flen [B, cap] - the largest, a number before NaN.  nfin NULL: every clip has one hypothesis - the
+ *   greedy decode with cap = 1, fscore = its scores, flen = its lengths.  nfin <= 0: 0.  The division Translator_ARFormer._norm
+ *   does on the host, bit for bit.  NULL fscore / flen / len_pow / out, B < 0, cap < 1, cap > 64, n_pow < 1 -> CARE_EINVAL;
+ *   len_pow / out not 8-byte aligned -> CARE_EALIGN; B == 0: a no-op.
+ */
+#define CARE_CORPUS_MAX_CAPTION 64
+#define CARE_CORPUS_BITMAP_WORDS 2048
+#define CARE_CORPUS_TOTALS 8
+#define CARE_CORPUS_N_CAPTIONS 0
+#define CARE_CORPUS_LENGTH_SUM 1
+#define CARE_CORPUS_N_DISTINCT 2
+#define CARE_CORPUS_N_NOVEL 3
+#define CARE_CORPUS_N_EMPTY 4
+#define CARE_CORPUS_USAGE 5
+#define CARE_CORPUS_N_OVERFLOW 6
+typedef struct care_corpus_bank {
+  const uint64_t* keys; const int64_t* start; const int32_t* tokens;
+  int64_t n;
+  uint64_t key_mask;
+} care_corpus_bank;
+typedef struct care_epoch_set {
+  int32_t* slots; int32_t* tokens; int32_t* length; uint64_t* keys;
+  uint32_t* bitmap; uint64_t* totals;
+  int32_t capacity; int32_t reserved;
+  uint64_t key_mask;
+} care_epoch_set;
+int care_corpus_insert(const int32_t* tokens, int ld, int col0, int width, const int32_t* length, int rows, int cursor, int eos,
+                       int pad, const care_corpus_bank* bank, const care_epoch_set* set, uint64_t* keys_out, void* stream);
+int care_corpus_totals(const care_epoch_set* set, void* stream);
+int care_caption_model_score(const int32_t* nfin, const float* fscore, const int32_t* flen, int B, int cap, const double* len_pow,
+                             int n_pow, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
