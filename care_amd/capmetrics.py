@@ -36,7 +36,8 @@ import torch
 
 from . import _lib
 from .constants import EOS
-from .reward import MAX_CAPTION, MAX_VOCAB, ORDERS, CiderBank, _need_device, pack_ngrams
+from .captions import caption_rows, need_device, number_words, strip_eos, upload
+from .reward import ORDERS, CiderBank, pack_ngrams
 
 __all__ = ["MetricBank", "corpus_scores", "check_metric_sum", "METRIC_SUM", "REC", "TOTALS"]
 
@@ -95,9 +96,7 @@ class MetricBank(object):
         for video in refs:
             keys, counts = [], []
             for ref in video:
-                toks = np.asarray(ref, dtype=np.int64).reshape(-1)
-                if toks.size and not self.with_eos and toks[-1] == EOS:
-                    toks = toks[:-1]
+                toks = strip_eos(ref, self.with_eos)
                 ref_tok.append(toks.astype(np.int32))
                 ref_tok_start.append(ref_tok_start[-1] + toks.size)
                 u, n = np.unique(np.concatenate([pack_ngrams(toks, k) for k in range(1, ORDERS + 1)]), return_counts=True)
@@ -118,15 +117,7 @@ class MetricBank(object):
         if self.device is None:
             return
 
-        def up(a):   # (at least one element, so that no array of the bank is a NULL pointer)
-            a = np.ascontiguousarray(a)
-            if a.dtype == np.uint64:
-                a = a.view(np.int64)
-            if a.size == 0:
-                a = np.zeros(1, dtype=a.dtype)
-            return torch.from_numpy(a.copy()).to(self.device)
-
-        self.dev = {k: up(a) for k, a in self.host.items()}
+        self.dev = {k: upload(a, self.device) for k, a in self.host.items()}
         self.desc = _lib.MetricBankDesc()
         ctypes.memmove(ctypes.addressof(self.desc), ctypes.addressof(c.desc), ctypes.sizeof(_lib.CiderBankDesc))
         for k, t in self.dev.items():
@@ -138,26 +129,10 @@ class MetricBank(object):
         """A bank from references given as lists of WORDS: a word of the model's vocabulary (`word_to_id`) gets its id, every
         other word a fresh id from `vocab_size` (default: the largest id of `word_to_id` + 1) upwards - `bank.extra_words`.
         More than 65536 ids in all is a ValueError (an n-gram's key holds 16 bits a token)."""
-        if vocab_size is None:
-            vocab_size = max(word_to_id.values()) + 1 if word_to_id else 1
-        extra, refs = {}, []
-        for video in refs_words:
-            of_video = []
-            for ref in video:
-                ids = []
-                for w in ref:
-                    i = word_to_id.get(w)
-                    if i is None:
-                        i = extra.get(w)
-                        if i is None:
-                            i = extra[w] = vocab_size + len(extra)
-                    ids.append(int(i))
-                of_video.append(ids)
-            refs.append(of_video)
-        total = vocab_size + len(extra)
-        if total > MAX_VOCAB:
-            raise ValueError("{} words outside the model's vocabulary of {}: {} ids in all > {} (an n-gram's key holds 16 bits "
-                             "a token)".format(len(extra), vocab_size, total, MAX_VOCAB))
+        videos = [list(video) for video in refs_words]
+        ids, extra, total = number_words([ref for video in videos for ref in video], word_to_id, vocab_size)
+        ids = iter(ids)
+        refs = [[next(ids) for _ in video] for video in videos]   # (video by video again)
         bank = cls(refs, total, with_eos=with_eos, device=device, video_ids=video_ids)
         bank.extra_words = extra
         return bank
@@ -176,23 +151,8 @@ class MetricBank(object):
         for.  tokens: int32 [rows, width <= 64 behind the offset] with unit stride in the last dimension and any row stride: a
         view such as fed[:, 1:] is scored in place (the rules of CiderBank.score)."""
         self._need_bank()
-        for what, t in (("tokens", tokens), ("length", length), ("video", video)):
-            _need_device(t, what)
-            if t.dtype != torch.int32:
-                raise TypeError("`{}` must be int32, got {}".format(what, t.dtype))
-        if tokens.dim() != 2 or tokens.stride(1) != 1:
-            raise ValueError("`tokens` must be [rows, width] with unit stride in the last dimension, got shape {} strides {}".format(
-                tuple(tokens.shape), tuple(tokens.stride())))
-        rows, width = tokens.shape[0], tokens.shape[1] - int(offset)
-        if offset < 0 or width < 1:
-            raise ValueError("`offset` {} leaves no column of `tokens` {}".format(offset, tuple(tokens.shape)))
-        if width > MAX_CAPTION:
-            raise ValueError("captions of up to {} tokens: care_caption_stats holds {}".format(width, MAX_CAPTION))
-        if length.numel() != rows or video.numel() != rows:
-            raise ValueError("`length` {} and `video` {} must hold one entry per row of `tokens` {}".format(
-                tuple(length.shape), tuple(video.shape), tuple(tokens.shape)))
-        length, video = length.contiguous(), video.contiguous()
-        ld = tokens.stride(0) if rows > 1 else max(tokens.stride(0), tokens.shape[1])
+        rows, width, ld, length = caption_rows(tokens, length, offset, "care_caption_stats", also=(("video", video),))
+        video = video.contiguous()
         stats = torch.empty(rows, REC, dtype=torch.int32, device=tokens.device)
         rouge = torch.empty(rows, dtype=torch.float64, device=tokens.device)
         with torch.cuda.device(tokens.device):
@@ -211,7 +171,7 @@ class MetricBank(object):
         batches; the two sums of doubles in a fixed order per batch, so they depend on the split in their last bits."""
         self._need_bank()
         stats, rouge, cider = rec["stats"], rec["rouge"], rec.get("cider")
-        _need_device(totals, "totals")
+        need_device(totals, "totals", "care_caption_totals")
         if totals.dtype != torch.int64 or totals.numel() != TOTALS or not totals.is_contiguous():
             raise ValueError("`totals` must be what new_totals() returned: a contiguous int64 tensor of {} words".format(TOTALS))
         rows = stats.shape[0]

@@ -31,9 +31,9 @@ EOS, is refused (the reference asserts the same, utils_corpora.py:432-433).  A s
 `opt["n_caps_per_video"]` is 0, else min(k, captions) of each video drawn once from RandomState(opt["seed"]).  `validate` /
 `test`: every video with its caption 0 (:418-419), frames equally sampled (:713-715).
 
-**Random numbers** are counter-based (h of csrc/sample.hip): an item's frames depend on (seed, epoch, the item's index in the
-infoset) alone - not on the batch or the batch size it falls into - and `loader` visits the `train` items of an epoch in
-ascending (h(item key, 0xFFFFFFFF), item).  The reference draws from numpy's / Python's global generators; its streams cannot
+**Random numbers** are counter-based (h = care_mix64 of csrc/care_common.h, `captions.mix64` here): an item's frames depend
+on (seed, epoch, the item's index in the infoset) alone - not on the batch or the batch size it falls into - and `loader`
+visits the `train` items of an epoch in ascending (h(item key, 0xFFFFFFFF), item).  The reference draws from numpy's / Python's global generators; its streams cannot
 be reproduced, the distributions and every deterministic rule are.
 
 There is no CPU fallback: a store built with device=None holds the host tables only (what the tests of the ingestion rules
@@ -46,6 +46,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .captions import mix64 as _mix
 from .constants import BOS, EOS, PAD
 from .data import N_TOTAL_FRAMES
 
@@ -55,15 +56,6 @@ ATTRIBUTE_START, ATTRIBUTE_END = 6, 3006   # config/Constants.py:15-16
 MODES = ("train", "validate", "test")
 SHUFFLE = 0xFFFFFFFF                        # the counter of an item's place in the epoch's order (no frame has it)
 _U = np.uint64
-
-
-def _mix(a, n):
-    """h(a, n) of csrc/sample.hip on uint64 arrays / scalars."""
-    with np.errstate(over="ignore"):
-        z = np.asarray(a, dtype=_U) + _U(0x9E3779B97F4A7C15) * (np.asarray(n, dtype=_U) + _U(1))
-        z = (z ^ (z >> _U(30))) * _U(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> _U(27))) * _U(0x94D049BB133111EB)
-        return z ^ (z >> _U(31))
 
 
 def snippet_bounds(n_total: int, n_frames: int):

@@ -32,39 +32,25 @@ import torch
 
 from . import _lib
 from .constants import EOS, PAD
-from .reward import MAX_CAPTION, MAX_VOCAB, _need_device
+from .captions import MAX_CAPTION, MAX_VOCAB, caption_rows, mix64, number_words, upload
 
 __all__ = ["CorpusBank", "EpochCaptions", "caption_key", "caption_keys", "analysis", "ALL_ONES", "TOTAL_NAMES"]
 
 ALL_ONES = (1 << 64) - 1
-GOLDEN = np.uint64(0x9E3779B97F4A7C15)
 TOTAL_NAMES = ("n_captions", "length_sum", "n_distinct", "n_novel", "n_empty", "usage", "n_overflow")   # care_hip.h: CARE_CORPUS_*
-
-
-def _fin(z: np.ndarray) -> np.ndarray:
-    """splitmix64's finaliser on a uint64 array, with wrap-around."""
-    z = z ^ (z >> np.uint64(30))
-    z = z * np.uint64(0xBF58476D1CE4E5B9)
-    z = z ^ (z >> np.uint64(27))
-    z = z * np.uint64(0x94D049BB133111EB)
-    return z ^ (z >> np.uint64(31))
-
-
-def _mix(a: np.ndarray, i: np.ndarray) -> np.ndarray:
-    return _fin(a + GOLDEN * (i + np.uint64(1)))
 
 
 def caption_keys(captions: Sequence[Sequence[int]], key_mask: int = ALL_ONES) -> np.ndarray:
     """uint64 [len(captions)]: the key csrc/corpus_stats.hip gives each caption (a sequence of ids, already cut) -
-    (h(n, 64) + sum_j h(token_j, j)) & key_mask in uint64 with wrap-around, h(a, i) = fin(a + 0x9E3779B97F4A7C15 (i + 1))."""
+    (h(n, 64) + sum_j h(token_j, j)) & key_mask in uint64 with wrap-around, h = captions.mix64."""
     lens = np.asarray([len(c) for c in captions], dtype=np.int64)
     with np.errstate(over="ignore"):
-        keys = _mix(lens.astype(np.uint64), np.full(lens.size, 64, dtype=np.uint64))
+        keys = mix64(lens, np.full(lens.size, 64, dtype=np.uint64))
         if lens.sum():
             flat = np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1) for c in captions]).astype(np.uint64)
             owner = np.repeat(np.arange(lens.size), lens)
             pos = (np.arange(flat.size) - np.repeat(np.cumsum(lens) - lens, lens)).astype(np.uint64)
-            np.add.at(keys, owner, _mix(flat, pos))
+            np.add.at(keys, owner, mix64(flat, pos))
     return keys & np.uint64(key_mask)
 
 
@@ -114,15 +100,7 @@ class CorpusBank(object):
         if self.device is None:
             return
 
-        def up(a):   # (at least one element, so that no array of the bank is a NULL pointer)
-            a = np.ascontiguousarray(a)
-            if a.dtype == np.uint64:
-                a = a.view(np.int64)
-            if a.size == 0:
-                a = np.zeros(1, dtype=a.dtype)
-            return torch.from_numpy(a.copy()).to(self.device)
-
-        self.dev = {k: up(a) for k, a in self.host.items()}
+        self.dev = {k: upload(a, self.device) for k, a in self.host.items()}
         self.desc = _lib.CorpusBankDesc()
         for k, t in self.dev.items():
             setattr(self.desc, k, t.data_ptr())
@@ -135,22 +113,7 @@ class CorpusBank(object):
         vocabulary (`word_to_id`) gets its id, every other word a fresh id from `vocab_size` upwards - `bank.extra_words`; the
         bank's vocab_size grows by their number (a TestEpoch wants it equal to its MetricBank's: build both from ids when the
         two word sets differ).  More than 65536 ids: a ValueError."""
-        if vocab_size is None:
-            vocab_size = max(word_to_id.values()) + 1 if word_to_id else 1
-        extra, caps = {}, []
-        for cap in train_words:
-            ids = []
-            for w in cap:
-                i = word_to_id.get(w)
-                if i is None:
-                    i = extra.get(w)
-                    if i is None:
-                        i = extra[w] = vocab_size + len(extra)
-                ids.append(int(i))
-            caps.append(ids)
-        total = vocab_size + len(extra)
-        if total > MAX_VOCAB:
-            raise ValueError("{} words outside the model's vocabulary of {}: {} ids in all > {}".format(len(extra), vocab_size, total, MAX_VOCAB))
+        caps, extra, total = number_words(train_words, word_to_id, vocab_size)
         bank = cls(caps, total, device=device, key_mask=key_mask)
         bank.extra_words = extra
         return bank
@@ -213,27 +176,12 @@ class EpochCaptions(object):
         """Adds caption r = tokens[r, offset : offset + length[r]], cut at the first EOS or PAD, for every row: two launches,
         nothing is waited for.  tokens: int32 [rows, width <= 64 behind the offset] with unit stride in the last dimension and
         any row stride (the rules of MetricBank.score).  Returns the store row of the batch's first caption."""
-        for what, t in (("tokens", tokens), ("length", length)):
-            _need_device(t, what)
-            if t.dtype != torch.int32:
-                raise TypeError("`{}` must be int32, got {}".format(what, t.dtype))
-        if tokens.dim() != 2 or tokens.stride(1) != 1:
-            raise ValueError("`tokens` must be [rows, width] with unit stride in the last dimension, got shape {} strides {}".format(
-                tuple(tokens.shape), tuple(tokens.stride())))
-        rows, width = tokens.shape[0], tokens.shape[1] - int(offset)
-        if offset < 0 or width < 1:
-            raise ValueError("`offset` {} leaves no column of `tokens` {}".format(offset, tuple(tokens.shape)))
-        if width > MAX_CAPTION:
-            raise ValueError("captions of up to {} tokens: care_corpus_insert holds {}".format(width, MAX_CAPTION))
-        if length.numel() != rows:
-            raise ValueError("`length` {} must hold one entry per row of `tokens` {}".format(tuple(length.shape), tuple(tokens.shape)))
+        rows, width, ld, length = caption_rows(tokens, length, offset, "care_corpus_insert")
         if self.cursor + rows > self.capacity:
             raise ValueError("{} captions after {}: the epoch is larger than its capacity {}".format(rows, self.cursor, self.capacity))
         if keys_out is not None and (keys_out.dtype != torch.int64 or keys_out.numel() != rows or not keys_out.is_contiguous()
                                      or keys_out.device != tokens.device):
             raise ValueError("`keys_out` must be a contiguous int64 tensor of {} words on the device".format(rows))
-        length = length.contiguous()
-        ld = tokens.stride(0) if rows > 1 else max(tokens.stride(0), tokens.shape[1])
         first = self.cursor
         with torch.cuda.device(tokens.device):
             _lib.call("care_corpus_insert", _lib.ptr(tokens), ld, int(offset), width, _lib.ptr(length), rows, first, EOS, PAD,

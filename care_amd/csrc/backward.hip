@@ -108,14 +108,10 @@ __global__ void act_kernel(const float* z, const float* dy, float* out, int64_t 
   else out[i] = dy[i] * (act == CARE_ACT_RELU ? (v > 0.f ? 1.f : 0.f) : (act == CARE_ACT_GELU ? b_gelu_grad(v) : 1.f));
 }
 
-// counter-based uniform in [0, 1): a 64-bit mix (splitmix64 finaliser) of (seed, element index) - stateless, so the
-// backward pass re-creates the forward's mask from the same (seed, index)
+// counter-based uniform in [0, 1): the top 24 bits of care_mix64(seed, element index) - stateless, so the backward pass
+// re-creates the forward's mask from the same (seed, index)
 __device__ __forceinline__ float b_uniform(unsigned long long seed, unsigned long long idx) {
-  unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (idx + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (float)(z >> 40) * (1.0f / 16777216.0f);
+  return (float)(care_mix64(seed, idx) >> 40) * (1.0f / 16777216.0f);
 }
 
 // out = x * keep / (1 - p), keep = uniform(seed, i) >= p  (nn.Dropout in training mode; the same call is its backward)

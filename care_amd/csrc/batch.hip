@@ -15,14 +15,6 @@ namespace {
 
 #define BST ((hipStream_t)stream)
 
-// h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin = the splitmix64 finaliser (csrc/sample.hip, smp_mix)
-__device__ __forceinline__ unsigned long long bt_mix(unsigned long long a, unsigned long long n) {
-  unsigned long long z = a + 0x9E3779B97F4A7C15ull * (n + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // ---------------------------------------------------------------------------------------------------------------- frame ids
 struct FrameBounds {
   int32_t b[CARE_BATCH_MAX_FRAMES + 1];
@@ -42,10 +34,11 @@ __global__ __launch_bounds__(BF_WAVES * 64) void frame_ids_kernel(const int32_t*
     for (int i = lane; i < n_frames; i += 64) o[i] = (bd.b[i] + bd.b[i + 1]) / 2;
     return;
   }
-  const unsigned long long k1 = bt_mix(bt_mix(seed, epoch), (unsigned long long)(long long)items[b]);
+  // (h = care_mix64: an item's frames depend on (seed, epoch, item) alone)
+  const unsigned long long k1 = care_mix64(care_mix64(seed, epoch), (unsigned long long)(long long)items[b]);
   if (type == CARE_FRAMES_SEGMENT) {
     for (int i = lane; i < n_frames; i += 64) {
-      const unsigned r = (unsigned)(bt_mix(k1, (unsigned long long)i) >> 32);
+      const unsigned r = (unsigned)(care_mix64(k1, (unsigned long long)i) >> 32);
       const unsigned w = (unsigned)(bd.b[i + 1] - bd.b[i]);
       o[i] = bd.b[i] + (int)(((unsigned long long)r * w) >> 32);
     }
@@ -53,7 +46,7 @@ __global__ __launch_bounds__(BF_WAVES * 64) void frame_ids_kernel(const int32_t*
   }
   // CARE_FRAMES_ALL: n_total <= 64, frame `lane`.  Lanes at or beyond n_total hold no frame: they are never counted, and
   // rank = n_total keeps them out of the ballot.
-  const unsigned long long key = bt_mix(k1, (unsigned long long)lane);
+  const unsigned long long key = care_mix64(k1, (unsigned long long)lane);
   const unsigned klo = (unsigned)key, khi = (unsigned)(key >> 32);
   int rank = 0;
   for (int g = 0; g < n_total; ++g) {

@@ -2,16 +2,17 @@
 // sufficient statistics of corpus BLEU and its ROUGE-L (care_caption_stats), their sum over an epoch in a totals block that
 // stays on the device (care_caption_totals), and the caption a beam search returns first (care_beam_winner).  int / fp32 /
 // double in both library variants; no floating-point atomics; a row's bits depend on the row alone (the rules of reward.hip).
+// The keys, the search, the ordered sums and the winner's order are csrc/caption_core.h's.
 //
-// The statistics: one workgroup of four waves per candidate.  The candidate's n-grams are the uint64 keys of
-// cider_score_kernel (16 bits a token, in LDS); the clipped counts come from the video's clip table - sorted unique keys with
+// The statistics: one workgroup of four waves per candidate.  The candidate's n-grams are the core's uint64 keys, the ones
+// CIDEr is scored on (16 bits a token, in LDS); the clipped counts come from the video's clip table - sorted unique keys with
 // the largest count over the video's references - by binary search, as integers.  The longest common subsequence is the
 // bit-parallel recurrence on ONE 64-bit word: lane j holds candidate token j, and per reference token t (uniform over the wave)
 //   M = ballot(cand[j] == t),  U = V & M,  V = (V + U) | (V & ~M),  V = ~0 at the start;
 // the LCS is the number of zero bits among the low L bits.  A ballot and four 64-bit integer operations per reference token, no
 // table, references of any length.  The waves take the video's references in turn; maxima of exact quotients and of integers
 // do not depend on that order.
-#include "care_common.h"
+#include "caption_core.h"
 
 // (a handful of double operations per row: each one rounded on its own, in both libraries)
 #pragma clang fp contract(off)
@@ -20,41 +21,13 @@ namespace {
 
 #define CST ((hipStream_t)stream)
 constexpr int CT = 256;          // threads of a statistics workgroup (4 waves)
-constexpr int CM_MAXLEN = 64;    // tokens of a caption
 constexpr int CM_REC = 12;       // ints of a record
 constexpr int TT = 1024;         // threads of the totals workgroup (16 waves)
 constexpr double BETA2 = 1.2 * 1.2;
 
-// first index in [lo, hi) whose key is >= k (hi when none)
-__device__ __forceinline__ int64_t cm_lower_bound(const uint64_t* keys, int64_t lo, int64_t hi, uint64_t k) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// the wave's sum by an inclusive scan in lane order (ONE tree of additions), lane 63's total to every lane
-__device__ __forceinline__ double cm_wave_scan_total(double v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return __shfl(v, 63, 64);
-}
-
-__device__ __forceinline__ long long cm_wave_sum_ll(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 struct StatsArgs {
-  const int32_t* tokens; int ld, col0, width;
-  const int32_t* length; const int32_t* video;
+  care_caption_rows cap;
+  const int32_t* video;
   int with_eos, eos;
   care_metric_bank bank;
   int32_t* rec; double* rouge;
@@ -68,14 +41,13 @@ __device__ __forceinline__ void cm_invalid_row(const StatsArgs& a, int r, int ti
 __global__ __launch_bounds__(CT) void caption_stats_kernel(StatsArgs a) {
   __shared__ uint64_t keys[CT];   // the candidate's n-grams: order 1 first, then 2, 3, 4, each in caption order
   __shared__ int clipc[CT];       // min(count in the candidate, clip table) at a key's FIRST occurrence, 0 elsewhere
-  __shared__ int tok[CM_MAXLEN];
+  __shared__ int tok[CARE_CAPTION_MAXLEN];
   __shared__ int correct[4];
   __shared__ int w_lcs[4], w_dist[4], w_len[4];
   __shared__ double w_rec[4];
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const care_metric_bank& bk = a.bank;
-  int L = a.length[r];
-  if (L > a.width) L = a.width;
+  int L = care_caption_len(a.cap, r);
   const int v = a.video[r];
   if (L <= 0 || v < 0 || v >= bk.cider.n_videos) {   // (uniform over the workgroup, like every exit below)
     cm_invalid_row(a, r, tid);
@@ -86,43 +58,21 @@ __global__ __launch_bounds__(CT) void caption_stats_kernel(StatsArgs a) {
     cm_invalid_row(a, r, tid);
     return;
   }
-  if (tid < L) tok[tid] = a.tokens[(int64_t)r * a.ld + a.col0 + tid] & 0xFFFF;
+  if (tid < L) tok[tid] = care_caption_token(a.cap, r, tid);
   __syncthreads();
   if (!a.with_eos && tok[L - 1] == (a.eos & 0xFFFF)) L -= 1;   // (L == 0 from here on: a legitimate empty caption)
 
   // ---- BLEU: the clipped counts of the four orders (order n, 0-based, owns the keys [base[n], base[n + 1]))
-  int base[5];
-  base[0] = 0;
-#pragma unroll
-  for (int n = 0; n < 4; ++n) base[n + 1] = base[n] + (L - n > 0 ? L - n : 0);
-  int ord = -1;
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-    if (tid >= base[n] && tid < base[n + 1]) ord = n;
-  int lo = 0, hi = 0;
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-    if (ord == n) { lo = base[n]; hi = base[n + 1]; }
-  if (ord >= 0) {
-    const int pos = tid - lo;
-    uint64_t k = 0;
-    for (int j = 0; j <= ord; ++j) k |= (uint64_t)(unsigned)tok[pos + j] << (16 * j);
-    keys[tid] = k;
-  }
-  __syncthreads();
+  int base[5], ord, lo, hi;
+  care_ngram_keys(tok, L, keys, base, ord, lo, hi);
   int c = 0;
   if (ord >= 0) {
     const uint64_t k = keys[tid];
-    int tf = 0;
-    bool first = true;
-    for (int j = lo; j < hi; ++j)
-      if (keys[j] == k) {
-        tf += 1;
-        if (j < tid) first = false;
-      }
+    bool first;
+    const int tf = care_ngram_tf(keys, lo, hi, k, first);
     if (first) {
       const int64_t cs = bk.clip_start[v], ce = bk.clip_start[v + 1];
-      const int64_t i = cm_lower_bound(bk.clip_keys, cs, ce, k);
+      const int64_t i = care_lower_bound(bk.clip_keys, cs, ce, k);
       if (i < ce && bk.clip_keys[i] == k) {
         const int m = bk.clip_max[i];
         c = tf < m ? tf : m;
@@ -217,9 +167,9 @@ __global__ __launch_bounds__(TT) void caption_totals_kernel(const int32_t* rec, 
     }
   }
 #pragma unroll
-  for (int k = 0; k < CM_REC; ++k) ai[k] = cm_wave_sum_ll(ai[k]);
-  ar = cm_wave_scan_total(ar);
-  ac = cm_wave_scan_total(ac);
+  for (int k = 0; k < CM_REC; ++k) ai[k] = care_wave_sum_64(ai[k]);
+  ar = care_wave_scan_total(ar);
+  ac = care_wave_scan_total(ac);
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < CM_REC; ++k) si[wave][k] = ai[k];
@@ -240,7 +190,7 @@ __global__ __launch_bounds__(TT) void caption_totals_kernel(const int32_t* rec, 
   }
 }
 
-// one wave per clip: lane i < min(nfin, cap) holds hypothesis i's normalised score; the best, the earliest among equals
+// one wave per clip: the tokens of the hypothesis care_beam_select names - the best normalised score, the earliest among equals
 __global__ __launch_bounds__(64) void beam_winner_kernel(const int32_t* nfin, const float* fscore, const int32_t* flen,
                                                          const int32_t* fhyp, int cap, int w, const double* len_pow, int n_pow,
                                                          int32_t* tokens, int32_t* length) {
@@ -253,31 +203,7 @@ __global__ __launch_bounds__(64) void beam_winner_kernel(const int32_t* nfin, co
     if (lane == 0) length[b] = 0;
     return;
   }
-  // the key of a stable ascending sort: -score / length ** alpha, NaN behind everything, +inf beyond the finished ones
-  double key = INFINITY;
-  bool have = false;
-  int len = 0;
-  if (lane < n) {
-    len = flen[(int64_t)b * cap + lane];
-    const int li = len < 0 ? 0 : (len > n_pow - 1 ? n_pow - 1 : len);
-    key = -((double)fscore[(int64_t)b * cap + lane] / len_pow[li]);
-    have = true;
-  }
-  int idx = lane;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ok = __shfl_xor(key, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    const int oh = __shfl_xor((int)have, o, 64);
-    // (a, i) before (b, j): a finished one before an empty lane, a number before NaN, the smaller key, the lower index
-    bool take;
-    if (oh != (int)have) take = oh != 0;
-    else if ((ok != ok) != (key != key)) take = key != key;
-    else if (ok < key) take = true;
-    else if (ok > key) take = false;
-    else take = oi < idx;
-    if (take) { key = ok; idx = oi; have = oh != 0; }
-  }
+  const int idx = care_beam_select(n, b, cap, fscore, flen, len_pow, n_pow).idx;
   int wl = flen[(int64_t)b * cap + idx];
   if (wl < 0) wl = 0;
   if (wl > w) wl = w;
@@ -285,8 +211,6 @@ __global__ __launch_bounds__(64) void beam_winner_kernel(const int32_t* nfin, co
   for (int j = lane; j < w; j += 64) out[j] = j < wl ? src[j] : 0;
   if (lane == 0) length[b] = wl;
 }
-
-inline bool cm_mis8(const void* p) { return (((uintptr_t)p) & 7u) != 0; }
 
 }  // namespace
 
@@ -298,12 +222,13 @@ extern "C" int care_caption_stats(const int32_t* tokens, int ld, int col0, int w
   if (!cb.vid_start || cb.n_videos < 1 || cb.n_refs < 0 || !bank->clip_keys || !bank->clip_max || !bank->clip_start ||
       !bank->ref_tok || !bank->ref_tok_start)
     return CARE_EINVAL;
-  if (width < 1 || width > CM_MAXLEN || col0 < 0 || (int64_t)ld < (int64_t)col0 + width) return CARE_EINVAL;
-  if (cm_mis8(bank->clip_keys) || cm_mis8(bank->clip_start) || cm_mis8(bank->ref_tok_start) || cm_mis8(rouge)) return CARE_EALIGN;
+  if (const int rc = care_caption_rows_check(ld, col0, width, CARE_EINVAL)) return rc;
+  if (!(care_aligned8(bank->clip_keys) && care_aligned8(bank->clip_start) && care_aligned8(bank->ref_tok_start) && care_aligned8(rouge)))
+    return CARE_EALIGN;
   if (rows == 0) return 0;
   StatsArgs a;
-  a.tokens = tokens; a.ld = ld; a.col0 = col0; a.width = width;
-  a.length = length; a.video = video;
+  a.cap = {tokens, ld, col0, width, length};
+  a.video = video;
   a.with_eos = with_eos; a.eos = eos;
   a.bank = *bank;
   a.rec = rec; a.rouge = rouge;
@@ -314,7 +239,7 @@ extern "C" int care_caption_stats(const int32_t* tokens, int ld, int col0, int w
 extern "C" int care_caption_totals(const int32_t* rec, const double* rouge, const float* cider, int rows, int64_t* totals_i,
                                    double* totals_d, void* stream) {
   if (!rec || !rouge || !totals_i || !totals_d || rows < 0) return CARE_EINVAL;
-  if (cm_mis8(rouge) || cm_mis8(totals_i) || cm_mis8(totals_d)) return CARE_EALIGN;
+  if (!(care_aligned8(rouge) && care_aligned8(totals_i) && care_aligned8(totals_d))) return CARE_EALIGN;
   if (rows == 0) return 0;
   hipLaunchKernelGGL(caption_totals_kernel, dim3(1), dim3(TT), 0, CST, rec, rouge, cider, rows, totals_i, totals_d);
   return care_launch_status();
@@ -324,7 +249,7 @@ extern "C" int care_beam_winner(const int32_t* nfin, const float* fscore, const 
                                 int w, const double* len_pow, int n_pow, int32_t* tokens, int32_t* length, void* stream) {
   if (!nfin || !fscore || !flen || !fhyp || !len_pow || !tokens || !length || B < 0) return CARE_EINVAL;
   if (cap < 1 || cap > 64 || w < 1 || n_pow < 1) return CARE_EINVAL;
-  if (cm_mis8(len_pow)) return CARE_EALIGN;
+  if (!care_aligned8(len_pow)) return CARE_EALIGN;
   if (B == 0) return 0;
   hipLaunchKernelGGL(beam_winner_kernel, dim3(B), dim3(64), 0, CST, nfin, fscore, flen, fhyp, cap, w, len_pow, n_pow, tokens, length);
   return care_launch_status();

@@ -59,6 +59,17 @@ static inline int care_launch_status() {
 }
 
 static inline bool care_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+static inline bool care_aligned8(const void* p) { return (((uintptr_t)p) & 7u) == 0; }   // (NULL counts as aligned)
+
+// h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin = the splitmix64 finaliser, in uint64 with wrap-around: the ONE
+// counter-based hash of the library - dropout masks (backward.hip), Gumbel noise (sample.hip), frame draws (batch.hip),
+// caption keys (corpus_stats.hip); care_amd/captions.py (mix64) restates it in numpy, bit for bit.
+__device__ __forceinline__ unsigned long long care_mix64(unsigned long long a, unsigned long long n) {
+  unsigned long long z = a + 0x9E3779B97F4A7C15ull * (n + 1);
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
 
 // Raise a kernel's dynamic-LDS limit, once per (kernel, device): `done` is a per-kernel bit mask
 // over device ordinals.  Safe from any thread: the attribute call is idempotent, so two racing first

@@ -10,8 +10,9 @@
 // One workgroup of four waves per clip: the keys and a bitmap of the positives (one ballot a chunk of 64 columns) in LDS, the
 // positives compacted in ascending column order (the bitmap's popcounts), dealt to the waves; for one positive the 64 lanes
 // sweep the K columns counting both integers (packed into one int), one wave reduction; rank is stored at slot posrank (the
-// posranks are a permutation of 0 .. P - 1).  AP = (sum_s (s + 1) / (rank[s] + 1)) / P in double, summed in one fixed order.
-#include "care_common.h"
+// posranks are a permutation of 0 .. P - 1).  AP = (sum_s (s + 1) / (rank[s] + 1)) / P in double, summed in one fixed order
+// (the lane-order scan of csrc/caption_core.h).
+#include "caption_core.h"
 
 // (each double operation rounded on its own, in both libraries)
 #pragma clang fp contract(off)
@@ -27,17 +28,6 @@ constexpr int QN = CARE_CONCEPT_MAX_TOPK;
 constexpr int TT = 1024;                         // threads of the totals workgroup (16 waves)
 
 struct TopK { int k[QN]; };
-
-// the wave's sum by an inclusive scan in lane order (ONE tree of additions), lane 63's total to every lane
-__device__ __forceinline__ double q_wave_scan_total(double v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return __shfl(v, 63, 64);
-}
 
 // clamp(p, 0.01, 0.99) as torch.clamp does it (NaN stays NaN), as a key that orders like the value with NaN on top
 __device__ __forceinline__ uint32_t q_key(float p) {
@@ -122,7 +112,7 @@ __global__ __launch_bounds__(QT) void concept_metrics_kernel(const float* preds,
   // AP: thread t owns the slots t, t + 256, ..; a scan in lane order; the waves in wave order
   double part = 0.0;
   for (int s = tid; s < P; s += QT) part += (double)(s + 1) / (double)(s_rank[s] + 1);
-  part = q_wave_scan_total(part);
+  part = care_wave_scan_total(part);
   if (lane == 0) s_sum[wave] = part;
   __syncthreads();
   if (tid == 0) {
@@ -167,7 +157,7 @@ __global__ __launch_bounds__(TT) void concept_totals_kernel(const double* ap, co
     empty += P == 0 ? 1 : 0;
   }
 #pragma unroll
-  for (int t = 0; t <= QN; ++t) a[t] = q_wave_scan_total(a[t]);
+  for (int t = 0; t <= QN; ++t) a[t] = care_wave_scan_total(a[t]);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     clips += __shfl_xor(clips, o, 64);
@@ -194,7 +184,6 @@ __global__ __launch_bounds__(TT) void concept_totals_kernel(const double* ap, co
   }
 }
 
-inline bool q_mis8(const void* p) { return (((uintptr_t)p) & 7u) != 0; }
 inline bool q_mis4(const void* p) { return (((uintptr_t)p) & 3u) != 0; }
 
 }  // namespace
@@ -213,7 +202,8 @@ extern "C" int care_concept_metrics(const float* preds, int64_t ldp, const float
   if (K > QK) return CARE_ESHAPE;
   for (int t = 0; t < n_topk; ++t)
     if (tk.k[t] > K) return CARE_ESHAPE;
-  if (q_mis4(preds) || q_mis4(labels) || q_mis4(hits) || q_mis4(n_pos) || q_mis8(ap) || q_mis8(totals_d) || q_mis8(totals_i))
+  if (q_mis4(preds) || q_mis4(labels) || q_mis4(hits) || q_mis4(n_pos) ||
+      !(care_aligned8(ap) && care_aligned8(totals_d) && care_aligned8(totals_i)))
     return CARE_EALIGN;
   if (B == 0) return 0;
   hipLaunchKernelGGL(concept_metrics_kernel, dim3(B), dim3(QT), 0, CST, preds, ldp, labels, ldl, K, tk, n_topk, ap, hits, n_pos);

@@ -7,8 +7,8 @@
 // A caption is a row of at most 64 tokens cut at the first EOS or PAD (to_sentence, misc/utils.py:117-137): ONE WAVE per
 // caption, token j on lane j.  Its key is a position-weighted sum in uint64 with wrap-around,
 //   key = (h(n, 64) + sum_j h(token_j, j)) & key_mask,   h(a, i) = fin(a + 0x9E3779B97F4A7C15 (i + 1)),  fin = splitmix64's finaliser
-// (csrc/batch.hip's mix; care_amd/corpusstats.py restates it in numpy, bit for bit): a commutative sum, so the order of the
-// wave's reduction does not matter.  Two captions are equal when their lengths are and a ballot of `token differs` is empty.
+// (h = care_mix64 of csrc/care_common.h; care_amd/captions.py restates it in numpy, bit for bit): a commutative sum, so the
+// order of the wave's reduction does not matter.  Two captions are equal when their lengths are and a ballot of `token differs` is empty.
 // A key only says where to look: every hit in the epoch set and in the training bank is confirmed token by token, so the
 // counts are exact, not exact up to collisions.
 //
@@ -19,7 +19,7 @@
 // name a row of an EARLIER launch or of launch (1) of this batch, which has completed before (2) starts: a reader of a slot
 // never sees a half-written row, and no fence is needed inside a launch.  Of equal captions exactly one wins a slot - which
 // one is a race, and nothing depends on it: the totals count captions, not rows.
-#include "care_common.h"
+#include "caption_core.h"
 
 namespace {
 
@@ -28,35 +28,10 @@ constexpr int CS_T = 256;                 // threads of a workgroup: four captio
 constexpr int CS_MAXLEN = CARE_CORPUS_MAX_CAPTION;
 constexpr int CS_WORDS = CARE_CORPUS_BITMAP_WORDS;
 constexpr int CS_POP_T = 1024;
-
-__device__ __forceinline__ uint64_t cs_fin(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-__device__ __forceinline__ uint64_t cs_mix(uint64_t a, uint64_t i) { return cs_fin(a + 0x9E3779B97F4A7C15ull * (i + 1ull)); }
-
-__device__ __forceinline__ uint64_t cs_wave_sum_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (uint64_t)__shfl_xor((long long)v, o, 64);
-  return v;
-}
-
-// first index in [0, n) whose key is >= k (n when none)
-__device__ __forceinline__ int64_t cs_lower_bound(const uint64_t* keys, int64_t n, uint64_t k) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
+static_assert(CS_MAXLEN == CARE_CAPTION_MAXLEN, "a store row holds one caption of the core's width");
 
 struct AppendArgs {
-  const int32_t* tokens; int ld, col0, width;
-  const int32_t* length;
+  care_caption_rows cap;
   int rows, cursor, eos, pad;
   care_epoch_set set;
   uint64_t* keys_out;
@@ -67,15 +42,14 @@ __global__ __launch_bounds__(CS_T) void corpus_append_kernel(AppendArgs a) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * (CS_T / 64) + (threadIdx.x >> 6);
   if (r >= a.rows) return;   // (uniform over the wave)
-  int L = a.length[r];
-  if (L > a.width) L = a.width;
+  int L = care_caption_len(a.cap, r);
   if (L < 0) L = 0;
   int tok = 0;
-  if (lane < L) tok = a.tokens[(int64_t)r * a.ld + a.col0 + lane] & 0xFFFF;
+  if (lane < L) tok = care_caption_token(a.cap, r, lane);
   const uint64_t stop = __ballot(lane < L && (tok == (a.eos & 0xFFFF) || tok == (a.pad & 0xFFFF)));
   const int n = stop ? (int)__builtin_ctzll(stop) : L;
-  const uint64_t part = lane < n ? cs_mix((uint64_t)(unsigned)tok, (uint64_t)lane) : 0ull;
-  const uint64_t key = (cs_wave_sum_u64(part) + cs_mix((uint64_t)n, 64ull)) & a.set.key_mask;
+  const uint64_t part = lane < n ? care_mix64((uint64_t)(unsigned)tok, (uint64_t)lane) : 0ull;
+  const uint64_t key = (care_wave_sum_64(part) + care_mix64((uint64_t)n, 64ull)) & a.set.key_mask;
   const int64_t g = (int64_t)a.cursor + r;
   a.set.tokens[g * CS_MAXLEN + lane] = lane < n ? tok : 0;
   if (lane == 0) {
@@ -134,7 +108,7 @@ __global__ __launch_bounds__(CS_T) void corpus_insert_kernel(InsertArgs a) {
   // the first of its kind this epoch: novel unless a training caption equals it - the run of equal keys, token by token
   const care_corpus_bank& bk = a.bank;
   bool found = false;
-  for (int64_t i = cs_lower_bound(bk.keys, bk.n, key); i < bk.n && bk.keys[i] == key; ++i) {
+  for (int64_t i = care_lower_bound(bk.keys, 0, bk.n, key); i < bk.n && bk.keys[i] == key; ++i) {
     const int64_t b0 = bk.start[i];
     const int64_t bn = bk.start[i + 1] - b0;
     if (bn != (int64_t)n) continue;
@@ -163,7 +137,7 @@ __global__ __launch_bounds__(CS_POP_T) void corpus_totals_kernel(care_epoch_set 
   }
 }
 
-// one wave per clip: lane i < min(nfin, cap) holds hypothesis i's normalised score; the value of care_beam_winner's choice
+// one wave per clip: the normalised score of the hypothesis care_beam_select names, the one care_beam_winner copies
 __global__ __launch_bounds__(64) void caption_model_score_kernel(const int32_t* nfin, const float* fscore, const int32_t* flen, int cap,
                                                                  const double* len_pow, int n_pow, double* out) {
   const int b = blockIdx.x, lane = threadIdx.x;
@@ -173,39 +147,15 @@ __global__ __launch_bounds__(64) void caption_model_score_kernel(const int32_t* 
     if (lane == 0) out[b] = 0.0;
     return;
   }
-  double key = INFINITY;
-  bool have = false;
-  if (lane < n) {
-    const int len = flen[(int64_t)b * cap + lane];
-    const int li = len < 0 ? 0 : (len > n_pow - 1 ? n_pow - 1 : len);
-    key = -((double)fscore[(int64_t)b * cap + lane] / len_pow[li]);
-    have = true;
-  }
-  int idx = lane;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ok = __shfl_xor(key, o, 64);
-    const int oi = __shfl_xor(idx, o, 64);
-    const int oh = __shfl_xor((int)have, o, 64);
-    // care_beam_winner's order: a finished one before an empty lane, a number before NaN, the smaller key, the lower index
-    bool take;
-    if (oh != (int)have) take = oh != 0;
-    else if ((ok != ok) != (key != key)) take = key != key;
-    else if (ok < key) take = true;
-    else if (ok > key) take = false;
-    else take = oi < idx;
-    if (take) { key = ok; idx = oi; have = oh != 0; }
-  }
+  const double key = care_beam_select(n, b, cap, fscore, flen, len_pow, n_pow).key;
   if (lane == 0) out[b] = -key;
 }
-
-inline bool cs_mis8(const void* p) { return (((uintptr_t)p) & 7u) != 0; }
 
 inline int cs_check_set(const care_epoch_set* s) {
   if (!s) return CARE_EINVAL;
   if (!s->slots || !s->tokens || !s->length || !s->keys || !s->bitmap || !s->totals) return CARE_EINVAL;
   if (s->capacity < 1 || (s->capacity & (s->capacity - 1)) != 0) return CARE_ESHAPE;
-  if (cs_mis8(s->keys) || cs_mis8(s->totals)) return CARE_EALIGN;
+  if (!(care_aligned8(s->keys) && care_aligned8(s->totals))) return CARE_EALIGN;
   return 0;
 }
 
@@ -218,16 +168,13 @@ extern "C" int care_corpus_insert(const int32_t* tokens, int ld, int col0, int w
   if (const int rc = cs_check_set(set)) return rc;
   if (!bank->keys || !bank->start || !bank->tokens || bank->n < 0) return CARE_EINVAL;
   if (bank->key_mask != set->key_mask) return CARE_EINVAL;   // (the bank's keys were masked on the host: one mask for both)
-  if (width < 1 || col0 < 0) return CARE_EINVAL;
-  if (width > CS_MAXLEN) return CARE_ESHAPE;
-  if ((int64_t)ld < (int64_t)col0 + width) return CARE_EINVAL;
+  if (const int rc = care_caption_rows_check(ld, col0, width, CARE_ESHAPE)) return rc;
   if ((int64_t)cursor + rows > (int64_t)set->capacity) return CARE_ESHAPE;
-  if (cs_mis8(bank->keys) || cs_mis8(bank->start) || cs_mis8(keys_out)) return CARE_EALIGN;
+  if (!(care_aligned8(bank->keys) && care_aligned8(bank->start) && care_aligned8(keys_out))) return CARE_EALIGN;
   if (rows == 0) return 0;
   const int blocks = (rows + CS_T / 64 - 1) / (CS_T / 64);
   AppendArgs ap;
-  ap.tokens = tokens; ap.ld = ld; ap.col0 = col0; ap.width = width;
-  ap.length = length;
+  ap.cap = {tokens, ld, col0, width, length};
   ap.rows = rows; ap.cursor = cursor; ap.eos = eos; ap.pad = pad;
   ap.set = *set;
   ap.keys_out = keys_out;
@@ -251,7 +198,7 @@ extern "C" int care_caption_model_score(const int32_t* nfin, const float* fscore
                                         const double* len_pow, int n_pow, double* out, void* stream) {
   if (!fscore || !flen || !len_pow || !out || B < 0) return CARE_EINVAL;
   if (cap < 1 || cap > 64 || n_pow < 1) return CARE_EINVAL;
-  if (cs_mis8(len_pow) || cs_mis8(out)) return CARE_EALIGN;
+  if (!(care_aligned8(len_pow) && care_aligned8(out))) return CARE_EALIGN;
   if (B == 0) return 0;
   hipLaunchKernelGGL(caption_model_score_kernel, dim3(B), dim3(64), 0, CST, nfin, fscore, flen, cap, len_pow, n_pow, out);
   return care_launch_status();

@@ -4,51 +4,30 @@
 // library variants.
 //
 // The reward: one workgroup of four waves per candidate caption.  A caption has at most 64 tokens, so at most 250 n-grams
-// (64 + 63 + 62 + 61) of orders 1..4, each ONE uint64 key: keys, weights and first-occurrence flags live in LDS (4 KB), only
-// the bank - the corpus' keys with ln df, the references' sorted keys and weights - is read from memory, by binary search.
-// Every sum is in double and in one order (the norms in key order, a reference's terms by a scan in lane order, a wave's
-// references in bank order, the waves in wave order): a row's bits depend on the row alone.  No atomics.
+// (64 + 63 + 62 + 61) of orders 1..4, each ONE uint64 key (csrc/caption_core.h builds them, for care_caption_stats too): keys,
+// weights and first-occurrence flags live in LDS (4 KB), only the bank - the corpus' keys with ln df, the references' sorted
+// keys and weights - is read from memory, by binary search.  Every sum is in double and in one order (the norms in key order,
+// a reference's terms by the core's scan in lane order, a wave's references in bank order, the waves in wave order): a row's
+// bits depend on the row alone.  No atomics.
 //
 // The loss: the row sweeps of csrc/vocab_row.h, which the language loss runs too, with a plain maximum as the visitor - a live
 // row is read once in the forward (in registers while V <= 12288) and once in the backward - and the weight of a row is its
 // sequence's advantage over the number of live positions, which stays on the device.
 #include "vocab_row.h"
+#include "caption_core.h"
 
-// the advantage has the bits of torch's elementwise fp32 operations: nothing is fused (vocab_row.h, above this line, holds
-// nothing that could be)
+// the advantage has the bits of torch's elementwise fp32 operations: nothing is fused (vocab_row.h and caption_core.h, above
+// this line, hold nothing that could be)
 #pragma clang fp contract(off)
 
 namespace {
 
 #define RST ((hipStream_t)stream)
 constexpr int RT = CARE_ROW_THREADS;   // threads of a workgroup (4 waves)
-constexpr int CID_MAXLEN = 64;         // tokens of a caption
-
-// the wave's sum by an inclusive scan in lane order (Hillis-Steele: lane l ends with v_0 + .. + v_l in ONE tree of additions),
-// lane 63's total to every lane.  All 64 lanes must be active.
-__device__ __forceinline__ double rw_wave_scan_total(double v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return __shfl(v, 63, 64);
-}
-
-// first index in [lo, hi) whose key is >= k (hi when none)
-__device__ __forceinline__ int64_t rw_lower_bound(const uint64_t* keys, int64_t lo, int64_t hi, uint64_t k) {
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (keys[mid] < k) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
 
 struct CiderArgs {
-  const int32_t* tokens; int ld, col0, width;
-  const int32_t* length; const int32_t* video;
+  care_caption_rows cap;
+  const int32_t* video;
   int with_eos, eos;
   care_cider_bank bank;
   float* out;
@@ -57,19 +36,18 @@ struct CiderArgs {
 __global__ __launch_bounds__(RT) void cider_score_kernel(CiderArgs a) {
   __shared__ uint64_t keys[RT];   // the candidate's n-grams: order 1 first, then 2, 3, 4, each in caption order
   __shared__ double wh[RT];       // tf (ln N - ln df) at a key's FIRST occurrence, 0 at its repeats and beyond the last key
-  __shared__ int tok[CID_MAXLEN];
+  __shared__ int tok[CARE_CAPTION_MAXLEN];
   __shared__ double normh[4];
   __shared__ double part[4][4];   // [wave][order]
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const care_cider_bank& bk = a.bank;
-  int L = a.length[r];
-  if (L > a.width) L = a.width;
+  int L = care_caption_len(a.cap, r);
   const int v = a.video[r];
   if (L <= 0 || v < 0 || v >= bk.n_videos) {   // (uniform over the workgroup, like every exit below)
     if (tid == 0) a.out[r] = 0.f;
     return;
   }
-  if (tid < L) tok[tid] = a.tokens[(int64_t)r * a.ld + a.col0 + tid] & 0xFFFF;
+  if (tid < L) tok[tid] = care_caption_token(a.cap, r, tid);
   __syncthreads();
   if (!a.with_eos && tok[L - 1] == (a.eos & 0xFFFF)) L -= 1;
   const int rb = bk.vid_start[v], re = bk.vid_start[v + 1];
@@ -77,39 +55,16 @@ __global__ __launch_bounds__(RT) void cider_score_kernel(CiderArgs a) {
     if (tid == 0) a.out[r] = 0.f;
     return;
   }
-  // order n (0-based) owns the keys [base[n], base[n + 1])
-  int base[5];
-  base[0] = 0;
-#pragma unroll
-  for (int n = 0; n < 4; ++n) base[n + 1] = base[n] + (L - n > 0 ? L - n : 0);
+  int base[5], ord, lo, hi;
+  care_ngram_keys(tok, L, keys, base, ord, lo, hi);
   const int K = base[4];   // <= 250
-  int ord = -1;
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-    if (tid >= base[n] && tid < base[n + 1]) ord = n;
-  int lo = 0, hi = 0;
-#pragma unroll
-  for (int n = 0; n < 4; ++n)
-    if (ord == n) { lo = base[n]; hi = base[n + 1]; }
-  if (ord >= 0) {
-    const int pos = tid - lo;
-    uint64_t k = 0;
-    for (int j = 0; j <= ord; ++j) k |= (uint64_t)(unsigned)tok[pos + j] << (16 * j);
-    keys[tid] = k;
-  }
-  __syncthreads();
   double w = 0.0;
   if (ord >= 0) {
     const uint64_t k = keys[tid];
-    int tf = 0;
-    bool first = true;
-    for (int j = lo; j < hi; ++j)
-      if (keys[j] == k) {
-        tf += 1;
-        if (j < tid) first = false;
-      }
+    bool first;
+    const int tf = care_ngram_tf(keys, lo, hi, k, first);
     if (first) {
-      const int64_t i = rw_lower_bound(bk.corpus_keys, 0, bk.n_corpus, k);
+      const int64_t i = care_lower_bound(bk.corpus_keys, 0, bk.n_corpus, k);
       const double lndf = (i < bk.n_corpus && bk.corpus_keys[i] == k) ? bk.corpus_lndf[i] : 0.0;   // absent: df = 0
       w = (double)tf * (bk.ln_n - lndf);
     }
@@ -131,7 +86,7 @@ __global__ __launch_bounds__(RT) void cider_score_kernel(CiderArgs a) {
       const double wi = wh[i];
       if (wi > 0.0) {   // a first occurrence with a weight: the others add exactly 0
         const uint64_t k = keys[i];
-        const int64_t j = rw_lower_bound(bk.ref_keys, ks, ke, k);
+        const int64_t j = care_lower_bound(bk.ref_keys, ks, ke, k);
         if (j < ke && bk.ref_keys[j] == k) {
           const double wr = bk.ref_w[j];
           const double t = fmin(wi, wr) * wr;
@@ -147,7 +102,7 @@ __global__ __launch_bounds__(RT) void cider_score_kernel(CiderArgs a) {
     const double* nr = bk.ref_norm + (int64_t)ref * 4;
 #define CID_ORDER(S, ACC, N)                                        \
   {                                                                 \
-    double t = rw_wave_scan_total(S);                               \
+    double t = care_wave_scan_total(S);                               \
     const double nh_ = normh[N], nr_ = nr[N];                       \
     if (nh_ != 0.0 && nr_ != 0.0) t /= (nh_ * nr_);                 \
     ACC += t * pen;                                                 \
@@ -271,7 +226,7 @@ __global__ __launch_bounds__(1024) void reward_loss_reduce_kernel(const float* l
       if (ad != 0.f) a += (double)ad * (double)logp[r];
     }
   }
-  a = rw_wave_scan_total(a);
+  a = care_wave_scan_total(a);
   c = care_wave_sum_i(c);
   if (lane == 0) { sa[wave] = a; sc[wave] = c; }
   __syncthreads();
@@ -316,8 +271,6 @@ __global__ __launch_bounds__(RT) void reward_loss_bwd_kernel(const float* logits
   care_row_map(x, d, sp, [=](float v, int c) { return cf * (expf((v - m) - ls) - (c == y ? 1.f : 0.f)); });
 }
 
-inline bool rw_mis8(const void* p) { return (((uintptr_t)p) & 7u) != 0; }
-
 }  // namespace
 
 extern "C" int care_cider_score(const int32_t* tokens, int ld, int col0, int width, const int32_t* length, const int32_t* video,
@@ -327,14 +280,14 @@ extern "C" int care_cider_score(const int32_t* tokens, int ld, int col0, int wid
   if (!bank->corpus_keys || !bank->corpus_lndf || !bank->ref_keys || !bank->ref_w || !bank->ref_start || !bank->ref_norm ||
       !bank->ref_len || !bank->vid_start || bank->n_videos < 1 || bank->n_refs < 0 || bank->n_corpus < 0)
     return CARE_EINVAL;
-  if (width < 1 || width > CID_MAXLEN || col0 < 0 || (int64_t)ld < (int64_t)col0 + width) return CARE_EINVAL;
-  if (rw_mis8(bank->corpus_keys) || rw_mis8(bank->corpus_lndf) || rw_mis8(bank->ref_keys) || rw_mis8(bank->ref_w) ||
-      rw_mis8(bank->ref_start) || rw_mis8(bank->ref_norm))
+  if (const int rc = care_caption_rows_check(ld, col0, width, CARE_EINVAL)) return rc;
+  if (!(care_aligned8(bank->corpus_keys) && care_aligned8(bank->corpus_lndf) && care_aligned8(bank->ref_keys) &&
+        care_aligned8(bank->ref_w) && care_aligned8(bank->ref_start) && care_aligned8(bank->ref_norm)))
     return CARE_EALIGN;
   if (rows == 0) return 0;
   CiderArgs a;
-  a.tokens = tokens; a.ld = ld; a.col0 = col0; a.width = width;
-  a.length = length; a.video = video;
+  a.cap = {tokens, ld, col0, width, length};
+  a.video = video;
   a.with_eos = with_eos; a.eos = eos;
   a.bank = *bank;
   a.out = out;
@@ -346,7 +299,7 @@ extern "C" int care_cider_score(const int32_t* tokens, int ld, int col0, int wid
 extern "C" int care_reward_advantage(const float* reward, const float* baseline, int B, int n, float* adv, double* stats,
                                      void* stream) {
   if (!reward || !adv || !stats || B < 1 || n < 1 || (!baseline && n < 2)) return CARE_EINVAL;
-  if (rw_mis8(stats)) return CARE_EALIGN;
+  if (!care_aligned8(stats)) return CARE_EALIGN;
   hipLaunchKernelGGL(reward_advantage_kernel, dim3(1), dim3(RT), 0, RST, reward, baseline, B, n, adv, stats);
   return care_launch_status();
 }
@@ -357,7 +310,7 @@ extern "C" int care_reward_loss_fwd(const float* logits, int64_t ld, int64_t seq
   // (whole sequences only; without a rows_per_seq to divide by the call is CARE_EINVAL whatever stands here)
   const int bad = care_row_check_fwd(logits && labels && adv && rmax && lsum && logp && totals && loss, logits, ld, seq_stride,
                                      rows_per_seq, V, rows, rows_per_seq > 0 && rows % rows_per_seq == 0,
-                                     !(rw_mis8(totals) || (acc && rw_mis8(acc))));
+                                     care_aligned8(totals) && care_aligned8(acc));
   if (bad) return bad;
 #define FWD_LAUNCH(N) hipLaunchKernelGGL(reward_loss_fwd_kernel<N>, dim3(rows), dim3(RT), 0, RST, logits, ld, seq_stride, rows_per_seq, V, labels, rmax, lsum, logp)
   if (V <= 4096) FWD_LAUNCH(4);
@@ -375,7 +328,7 @@ extern "C" int care_reward_loss_bwd(const float* logits, int64_t ld, int64_t seq
                                     int seq_rows, int rows, void* stream) {
   unsigned grid = 0;
   const int bad = care_row_check_bwd(logits && labels && adv && rmax && lsum && totals && g && dlogits, logits, ld, seq_stride,
-                                     rows_per_seq, V, dlogits, ldd, dseq_stride, seq_rows, rows, true, !rw_mis8(totals), &grid);
+                                     rows_per_seq, V, dlogits, ldd, dseq_stride, seq_rows, rows, true, care_aligned8(totals), &grid);
   if (bad) return bad;
   hipLaunchKernelGGL(reward_loss_bwd_kernel, dim3(grid), dim3(RT), 0, RST, logits, ld, seq_stride, rows_per_seq, V, labels,
                      adv, rmax, lsum, totals, g, dlogits, ldd, dseq_stride, seq_rows);

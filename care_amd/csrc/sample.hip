@@ -42,14 +42,6 @@ __device__ __forceinline__ float smp_unord(unsigned k) {
   return __builtin_bit_cast(float, (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-// h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin = the splitmix64 finaliser (csrc/backward.hip, b_uniform)
-__device__ __forceinline__ unsigned long long smp_mix(unsigned long long a, unsigned long long n) {
-  unsigned long long z = a + 0x9E3779B97F4A7C15ull * (n + 1);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 struct SampleParams {   // the 24-byte device block of care_sample_logits
   unsigned long long seed;
   float inv_temperature, top_p;
@@ -282,9 +274,9 @@ __global__ __launch_bounds__(1024) void sample_logits_kernel(const SampleArgs p)
 
   // ---- Gumbel-max over the kept set; ties to the lower index
   const unsigned rk = p.row_key ? (unsigned)p.row_key[row] : (unsigned)row;
-  const unsigned long long rs = smp_mix(seed, ((unsigned long long)rk << 16) | (unsigned long long)(unsigned)p.t);
+  const unsigned long long rs = care_mix64(seed,((unsigned long long)rk << 16) | (unsigned long long)(unsigned)p.t);
   auto perturbed = [&](unsigned k, int i) -> float {
-    const unsigned kk = (unsigned)(smp_mix(rs, (unsigned long long)i) >> 41);     // the top 23 bits
+    const unsigned kk = (unsigned)(care_mix64(rs, (unsigned long long)i) >> 41);  // the top 23 bits
     const float u = (float)(2u * kk + 1u) * (1.0f / 16777216.0f);                   // exact, in (0, 1)
     return smp_unord(k) + (-logf(-logf(u)));
   };

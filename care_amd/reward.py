@@ -25,13 +25,12 @@ import numpy as np
 import torch
 
 from . import _lib
+from .captions import MAX_CAPTION, MAX_VOCAB, caption_rows, need_device, strip_eos, upload  # noqa: F401 (the two limits: re-exported)
 from .constants import EOS, PAD
 from .criterion import DeferredLogits, _seq_rows, _seq_rows_grad
 
 __all__ = ["CiderBank", "reward_advantage", "self_critical_loss", "pack_ngrams", "MAX_CAPTION"]
 
-MAX_CAPTION = 64      # tokens of a candidate caption (csrc/reward.hip: 250 n-grams in LDS)
-MAX_VOCAB = 1 << 16   # 16 bits a token in an n-gram's key
 ORDERS = 4
 
 
@@ -51,13 +50,6 @@ def key_order(keys: np.ndarray) -> np.ndarray:
     """The order (1..4) of packed keys: the highest non-zero 16-bit group (no token inside a caption is 0)."""
     keys = np.asarray(keys, dtype=np.uint64)
     return ((keys >> np.uint64(16)) != 0).astype(np.int64) + ((keys >> np.uint64(32)) != 0) + ((keys >> np.uint64(48)) != 0) + 1
-
-
-def _need_device(t, what: str) -> None:
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("`{}` must be a tensor, got {}".format(what, type(t).__name__))
-    if t.device.type != "cuda":
-        raise RuntimeError("`{}` is on `{}`: the reward and its loss run on the MI355X (no CPU fallback)".format(what, t.device))
 
 
 class CiderBank(object):
@@ -89,9 +81,7 @@ class CiderBank(object):
         for v, video in enumerate(refs):
             of_video = []
             for ref in video:
-                toks = np.asarray(list(ref), dtype=np.int64).reshape(-1)
-                if toks.size and not self.with_eos and toks[-1] == EOS:
-                    toks = toks[:-1]
+                toks = strip_eos(ref, self.with_eos)
                 if toks.size and (toks.min() <= PAD or toks.max() >= vocab_size):
                     raise ValueError("video {}: a reference holds a token outside [1, vocab_size = {})".format(v, vocab_size))
                 keys = np.concatenate([pack_ngrams(toks, n) for n in range(1, ORDERS + 1)])
@@ -122,22 +112,12 @@ class CiderBank(object):
                      "vid_start": np.asarray(vid_start, dtype=np.int32)}
         self.n_refs = len(ref_keys)
 
-        def up(a, dtype):   # (at least one element, so that no array of the bank is a NULL pointer)
-            a = np.ascontiguousarray(a)
-            if a.dtype == np.uint64:
-                a = a.view(np.int64)
-            if a.size == 0:
-                a = np.zeros(1, dtype=a.dtype)
-            return torch.from_numpy(a.copy()).to(dtype).to(self.device)
-
-        h = self.host
         self.dev = self.desc = None
         if self.device is None:
             return
-        self.dev = {"corpus_keys": up(h["corpus_keys"], torch.int64), "corpus_lndf": up(h["corpus_lndf"], torch.float64),
-                    "ref_keys": up(h["ref_keys"], torch.int64), "ref_w": up(h["ref_w"], torch.float64),
-                    "ref_start": up(h["ref_start"], torch.int64), "ref_norm": up(h["ref_norm"].reshape(-1), torch.float64),
-                    "ref_len": up(h["ref_len"], torch.int32), "vid_start": up(h["vid_start"], torch.int32)}
+        dtypes = {"corpus_keys": torch.int64, "corpus_lndf": torch.float64, "ref_keys": torch.int64, "ref_w": torch.float64,
+                  "ref_start": torch.int64, "ref_norm": torch.float64, "ref_len": torch.int32, "vid_start": torch.int32}
+        self.dev = {k: upload(self.host[k].reshape(-1), self.device, dt) for k, dt in dtypes.items()}
         self.desc = self._desc()
 
     def _desc(self) -> "_lib.CiderBankDesc":
@@ -170,23 +150,8 @@ class CiderBank(object):
         fed[:, 1:] is scored in place.  bad (optional, int32 [1]): the number of rows whose video is outside the bank."""
         if self.desc is None:
             raise RuntimeError("this bank was built with device=None (host tables only): CIDEr-D is scored on the MI355X")
-        for what, t in (("tokens", tokens), ("length", length), ("video", video)):
-            _need_device(t, what)
-            if t.dtype != torch.int32:
-                raise TypeError("`{}` must be int32, got {}".format(what, t.dtype))
-        if tokens.dim() != 2 or tokens.stride(1) != 1:
-            raise ValueError("`tokens` must be [rows, width] with unit stride in the last dimension, got shape {} strides {}".format(
-                tuple(tokens.shape), tuple(tokens.stride())))
-        rows, width = tokens.shape[0], tokens.shape[1] - int(offset)
-        if offset < 0 or width < 1:
-            raise ValueError("`offset` {} leaves no column of `tokens` {}".format(offset, tuple(tokens.shape)))
-        if width > MAX_CAPTION:
-            raise ValueError("captions of up to {} tokens: care_cider_score holds {}".format(width, MAX_CAPTION))
-        if length.numel() != rows or video.numel() != rows:
-            raise ValueError("`length` {} and `video` {} must hold one entry per row of `tokens` {}".format(
-                tuple(length.shape), tuple(video.shape), tuple(tokens.shape)))
-        length, video = length.contiguous(), video.contiguous()
-        ld = tokens.stride(0) if rows > 1 else max(tokens.stride(0), tokens.shape[1])
+        rows, width, ld, length = caption_rows(tokens, length, offset, "care_cider_score", also=(("video", video),))
+        video = video.contiguous()
         if out is None:
             out = torch.empty(rows, dtype=torch.float32, device=tokens.device)
         elif out.dtype != torch.float32 or out.numel() != rows or not out.is_contiguous() or out.device != tokens.device:
@@ -201,14 +166,14 @@ def reward_advantage(reward: torch.Tensor, baseline: Optional[torch.Tensor] = No
     """(adv fp32 [B, n], stats float64 [2]) of reward [B, n]: adv = reward - baseline[b] with `baseline` [B] (the greedy
     caption's reward), else reward minus the mean of the clip's OTHER n - 1 samples; stats = the mean reward and the mean
     baseline, device doubles."""
-    _need_device(reward, "reward")
+    need_device(reward, "reward", "care_reward_advantage")
     if reward.dim() != 2 or reward.dtype != torch.float32:
         raise ValueError("`reward` must be fp32 [clips, samples], got {} {}".format(reward.dtype, tuple(reward.shape)))
     B, n = reward.shape
     if baseline is None and n < 2:
         raise ValueError("the leave-one-out baseline needs n_samples >= 2, got {}".format(n))
     if baseline is not None:
-        _need_device(baseline, "baseline")
+        need_device(baseline, "baseline", "care_reward_advantage")
         if baseline.dtype != torch.float32 or baseline.numel() != B:
             raise ValueError("`baseline` must be fp32 [{}], got {} {}".format(B, baseline.dtype, tuple(baseline.shape)))
         baseline = baseline.contiguous()
@@ -264,7 +229,7 @@ def self_critical_loss(logits, labels, advantages, acc: Optional[torch.Tensor] =
             "`logits` is a DeferredLogits: the fused head (set_fused_head(True)) never materialises the [N, t, V] logits the "
             "self-critical loss is taken over - call set_fused_head(False) on the module")
     for what, t in (("logits", logits), ("labels", labels), ("advantages", advantages)):
-        _need_device(t, what)
+        need_device(t, what, "the self-critical loss")
     if logits.dtype != torch.float32:
         raise TypeError("`logits` must be fp32, got {}".format(logits.dtype))
     if logits.dim() != 3 or labels.dim() != 2 or labels.shape[0] != logits.shape[0] or \

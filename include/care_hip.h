@@ -1163,8 +1163,8 @@ int care_concept_metrics(const float* preds, int64_t ldp, const float* labels, i
  * Dataset.__getitem__ + default_collate + H2D copy (dataloader.py:142-190, :232-262, :352-384, :777-814).  Integer and byte
  * arithmetic only: the same in both library variants; nothing synchronises; plain vector stores throughout.
  *
- * The counter-based generator is csrc/sample.hip's mix:  h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin = the splitmix64
- * finaliser, all in uint64 with wrap-around.  Item key k1 = h(h(seed, epoch), item), `item` = items[b] - the item's index in
+ * The counter-based generator is csrc/care_common.h's care_mix64:  h(a, n) = fin(a + 0x9E3779B97F4A7C15 (n + 1)), fin = the
+ * splitmix64 finaliser, all in uint64 with wrap-around.  Item key k1 = h(h(seed, epoch), item), `item` = items[b] - the item's index in
  * the store's infoset, NOT its place b in the batch: an item gets the same frames in whatever batch it lies.
  *
  * care_batch_frame_ids (dataloader.py:23-31 get_frame_ids): frame_ids int32 [B, n_frames], ascending per item.  `bounds` is a
