@@ -92,7 +92,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* x, int64_t ldx
 }
 
 // ------------------------------------------------------------------ activation, dropout
-__device__ __forceinline__ float b_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 __device__ __forceinline__ float b_gelu_grad(float v) {
   const float cdf = 0.5f * (1.0f + erff(v * 0.70710678118654752440f));
   const float pdf = 0.39894228040143267794f * expf(-0.5f * v * v);
@@ -104,7 +103,7 @@ __global__ void act_kernel(const float* z, const float* dy, float* out, int64_t 
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float v = z[i];
-  if (!dy) out[i] = act == CARE_ACT_RELU ? fmaxf(v, 0.f) : (act == CARE_ACT_GELU ? b_gelu(v) : v);
+  if (!dy) out[i] = act == CARE_ACT_RELU ? fmaxf(v, 0.f) : (act == CARE_ACT_GELU ? care_gelu(v) : v);
   else out[i] = dy[i] * (act == CARE_ACT_RELU ? (v > 0.f ? 1.f : 0.f) : (act == CARE_ACT_GELU ? b_gelu_grad(v) : 1.f));
 }
 

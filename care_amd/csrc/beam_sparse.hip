@@ -12,7 +12,7 @@
 // ~2 % of the dense pass's arithmetic.  The candidate lists then go to care_beam_pick as before.
 #include <cstdlib>
 
-#include "care_common.h"
+#include "gemm_stream.h"
 
 #ifndef SP_BLOCKS_DEF
 #define SP_BLOCKS_DEF 1024
@@ -20,10 +20,8 @@
 
 namespace {
 
-constexpr int SP_N = 32;       // columns per tile (gemm_vocab.hip's VT_N)
+constexpr int SP_N = GS_N32;   // columns per tile: the 32-row image of csrc/gemm_stream.h, as in pass 1
 constexpr int SP_BLOCKS = SP_BLOCKS_DEF;  // persistent workgroups of the recompute launch
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __global__ void sparse_zero_kernel(int32_t* tcount, int tiles) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -103,11 +101,11 @@ struct SpArgs {
   int M, N;
 };
 
-constexpr int SP_LDS = 32 * 1024;  // the W tile
+constexpr int SP_LDS = GS_TILE32;  // the W tile
 
 // Persistent workgroups over the work units (tile, 128 consecutive entries of the tile's list): wave w of the workgroup takes
-// 32 of them.  The W tile goes through LDS once per unit (whole 1-KB rows by LDS-DMA, swizzled like gemm_vocab.hip's
-// ring; kept when the next unit is of the same tile); the listed activation rows are gathered straight into the fragments
+// 32 of them.  The W tile goes through LDS once per unit (whole 1-KB rows by LDS-DMA, the image of pass 1's ring slots:
+// gemm_stream.h; kept when the next unit is of the same tile); the listed activation rows are gathered straight into the fragments
 // (lane = row: 16-byte pieces of 32 different rows per load instruction - slow per wave, but with 32 KB of LDS two
 // workgroups share a CU; staging them in LDS too, one workgroup per CU, took 109 us, both operands gathered 168 us).
 __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
@@ -115,9 +113,8 @@ __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 31, h = lane >> 5;
   const int total = p.unit_start[p.tiles];
-  // fragment offset inside the 32-row image: row r, chunk (2 ks + h) ^ (r & 15) (gemm_vocab.hip `boff`)
-  const int bswz = r * 1024;
-  auto boff = [&](int ks) { return bswz + ((((2 * ks + h) ^ (r & 15)) & 15) << 4) + ((2 * ks) >> 4) * 256; };
+  const int bswz = r * GS_ROW;
+  auto boff = [&](int ks) { return bswz + gs_frag32(r, h, ks); };
   int staged = -1;
   for (int u = blockIdx.x; u < total; u += gridDim.x) {
     int lo = 0, hi = p.tiles - 1;  // the tile of unit u: the last one whose first unit is <= u
@@ -133,10 +130,8 @@ __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) {  // wave w copies rows 8w .. 8w + 7; rows past N clamped, their columns are masked below
         const int n = wave * 8 + i;
-        const unsigned char* g = reinterpret_cast<const unsigned char*>(p.W) + (int64_t)min(tile * SP_N + n, p.N - 1) * 1024 +
-                                 ((lane ^ (n & 15)) << 4);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                         (__attribute__((address_space(3))) void*)(smem + n * 1024), 16, 0, 0);
+        gs_dma_row(reinterpret_cast<const unsigned char*>(p.W) + (int64_t)min(tile * SP_N + n, p.N - 1) * GS_ROW + gs_src_chunk(lane, n),
+                   smem + n * GS_ROW);
       }
     }
     const bool live = e0 < count;
@@ -150,7 +145,7 @@ __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
     if (!live) continue;
     const bf16_t* arow = p.A + (int64_t)row * p.lda + h * 8;
     const float th = p.thr[row];
-    f32x16 acc;
+    care_f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
     // The activation fragments come in two batches of 16, every load of a batch in flight before its first MFMA
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
     unsigned hits = 0;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int c = tile * SP_N + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int c = tile * SP_N + gs_col32(i, h);
       if (valid && c < p.N && acc[i] >= th) hits |= 1u << i;
     }
     if (hits) {
@@ -182,7 +177,7 @@ __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
         if (hits & (1u << i)) {
           if (pos < p.cap) {
             p.cval[(int64_t)row * p.cap + pos] = acc[i];
-            p.cidx[(int64_t)row * p.cap + pos] = tile * SP_N + (i & 3) + 8 * (i >> 2) + 4 * h;
+            p.cidx[(int64_t)row * p.cap + pos] = tile * SP_N + gs_col32(i, h);
           }
           ++pos;
         }
@@ -191,8 +186,6 @@ __global__ __launch_bounds__(256) void sparse_collect_kernel(SpArgs p) {
 }
 
 }  // namespace
-
-extern "C" int care_vocab32_applies(int M, int N, int K, int a_dtype, int has_labels);
 
 // Whether the sparse second pass covers the shape (the 256-row statistics kernel writes the tile maxima).
 extern "C" int care_beam_sparse_applies(int M, int N, int K, int a_dtype) {

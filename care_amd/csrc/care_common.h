@@ -71,6 +71,51 @@ __device__ __forceinline__ unsigned long long care_mix64(unsigned long long a, u
   return z ^ (z >> 31);
 }
 
+// exact GELU (the erf form), the activation of every dense layer that has one
+__device__ __forceinline__ float care_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
+
+// Counted waits.  s_waitcnt takes immediates, so a count known at compile time is a template argument.  care_wait_vm
+// lets lgkmcnt(0) ride along (this wave's LDS traffic is complete before the barrier that follows), care_wait_vmcnt
+// waits for the vector-memory counter alone.
+template <int N>
+__device__ __forceinline__ void care_wait_vm() {
+  static_assert(N >= 0 && N <= 63, "vmcnt immediate");
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void care_wait_vmcnt() {
+  static_assert(N >= 0 && N <= 63, "vmcnt immediate");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+// A run-time count: dispatch over the even counts from ELSE (or 2) to 20 - DMA rows and vector stores come in pairs.
+// ELSE is the caller's floor, the count that is outstanding at least: any other value waits for ELSE (a case below it
+// falls through to the default).
+template <int ELSE>
+__device__ __forceinline__ void care_wait_vm_even(int n) {
+#define CARE_WAIT_CASE(K) case K: if constexpr (K >= ELSE) { care_wait_vm<K>(); break; }
+  switch (n) {
+    CARE_WAIT_CASE(20) CARE_WAIT_CASE(18) CARE_WAIT_CASE(16) CARE_WAIT_CASE(14) CARE_WAIT_CASE(12)
+    CARE_WAIT_CASE(10) CARE_WAIT_CASE(8) CARE_WAIT_CASE(6) CARE_WAIT_CASE(4) CARE_WAIT_CASE(2)
+    default: care_wait_vm<ELSE>();
+  }
+#undef CARE_WAIT_CASE
+}
+
+// In-kernel timeline of a TOOLS build (tools/variant_lib.py and tools/*_ts.py, behind a file's *_DBG & 64 switch):
+// CARE_STAMPS(name, waves) at file scope defines the array name_stamps[wave][64 steps][4] and its getter
+// care_<name>_stamps; CARE_STAMP(name, waves, step, k) in a kernel with `lane` and `wave` in scope has workgroup 0
+// write s_memtime into slot k of (wave, step).
+#define CARE_STAMPS(NAME, WAVES)                                        \
+  __device__ unsigned long long NAME##_stamps[(WAVES) * 64 * 4];        \
+  extern "C" int care_##NAME##_stamps(void* out) {                      \
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(NAME##_stamps), sizeof(NAME##_stamps)); \
+  }
+#define CARE_STAMP(NAME, WAVES, step, k)                                                                        \
+  do {                                                                                                          \
+    if (blockIdx.x == 0 && blockIdx.y == 0 && (step) < 64 && lane == 0 && wave < (WAVES))                       \
+      NAME##_stamps[(wave * 64 + (step)) * 4 + (k)] = __builtin_amdgcn_s_memtime();                             \
+  } while (0)
+
 // Raise a kernel's dynamic-LDS limit, once per (kernel, device): `done` is a per-kernel bit mask
 // over device ordinals.  Safe from any thread: the attribute call is idempotent, so two racing first
 // callers at worst both make it.  Returns 0 or the hipError_t.

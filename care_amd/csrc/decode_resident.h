@@ -241,7 +241,7 @@ struct GridSync {
 
 __device__ __forceinline__ float res_act(float v, int act) {
   if (act == CARE_ACT_RELU) return fmaxf(v, 0.0f);
-  if (act == CARE_ACT_GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+  if (act == CARE_ACT_GELU) return care_gelu(v);
   return v;
 }
 

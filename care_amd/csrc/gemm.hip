@@ -41,7 +41,7 @@ template <> struct KTraits<bf16_t> { static constexpr int BK = 64; };
 // most of the 128 x 128 kernel's 7800 instructions: see csrc/gemm_tile.hip, tile_epilogue)
 template <bool GELU>
 __device__ __forceinline__ float apply_act(float v, int act) {
-  if constexpr (GELU) return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+  if constexpr (GELU) return care_gelu(v);
   return act == CARE_ACT_RELU ? fmaxf(v, 0.0f) : v;
 }
 

@@ -2,22 +2,12 @@
 //
 // Almost every GEMM of the path has K = d_model = 512 (QKV, Wq, Wo, FFN1, cross-K/V, vocab)
 // and a tall-skinny or huge-N shape.  A classic LDS-tiled kernel re-stages A for every
-// N-tile and synchronises every k-step; at K = 512 that is all prologue.  Here instead:
+// N-tile and synchronises every k-step; at K = 512 that is all prologue.  Here instead the
+// scheme of csrc/gemm_stream.h (resident A, ring of W tiles, swizzled image, counted waits):
 //
-//   * a workgroup owns a panel of 128 rows (4 waves x 32 rows).  Each wave loads the MFMA
-//     A-fragments of its 32 rows for the whole K (<= 512) ONCE, straight from global memory
-//     into 128 VGPRs (all 32 loads in flight at once), and keeps them there;
-//   * W is streamed in tiles of 16 output columns x 512 k (16 KiB) through a 4-deep LDS ring
-//     filled by LDS-DMA (global_load_lds, 16 B per lane, one 1-KiB W row per
-//     wave-instruction) with THREE tiles in flight: the DMA latency (~2 us under load) is
-//     several times the 32 MFMAs a wave spends on a tile, so one tile of prefetch leaves the
-//     kernel latency-bound (measured: 18 % MFMA occupancy).  Waits are counted
-//     (s_waitcnt vmcnt(N) with N = the exact number of younger VM operations, output stores
-//     included) and the barrier is a raw s_barrier, so neither the in-flight DMA nor the
-//     previous tiles' stores are drained;
-//   * the LDS image is lane-linear, so the bank-conflict swizzle (16-byte chunk ^= row & 15)
-//     is applied to the per-lane SOURCE address and again on the ds_read_b128 of the B
-//     fragment (conflict-free for every 16-lane read group);
+//   * a workgroup owns a panel of 128 rows (4 waves x 32 rows), the A-fragments of a wave's
+//     32 rows for the whole K (<= 512) in 128 VGPRs;
+//   * W is streamed in tiles of 16 output columns x 512 k (16 KiB);
 //   * in the store mode the MFMA operands are swapped (D = tile of (A W^T)^T), so a lane holds
 //     4 consecutive output columns of one row: one 16-byte (fp32) / 8-byte (bf16) store per
 //     16x16 tile per lane;
@@ -32,7 +22,7 @@
 // Requires K % 128 == 0 and K <= 512 per slice.
 #include <cstdlib>
 
-#include "care_common.h"
+#include "gemm_stream.h"
 
 // Ablation builds only (tools/gemm_bench.py): -DCARE_AS_DBG=<bits> 1 no stores, 2 no MFMA, 4 no W DMA, 16 no argmax statistics, 32 no B-fragment LDS reads,
 // 8 no A loads.  Compile-time so that the shipped kernel carries no debug branches.
@@ -47,9 +37,8 @@ namespace {
 enum { STREAM_STORE = 0, STREAM_ARGMAX = 1, STREAM_ARGMAX_LAB = 2, STREAM_COLLECT = 3 };
 
 constexpr int TILE_N = 16;             // output columns per W tile
-constexpr int TILE_BYTES = TILE_N * 1024;
-constexpr int RING = 4;                // LDS ring slots
-constexpr int AHEAD = 3;               // tiles in flight
+constexpr int TILE_BYTES = TILE_N * GS_ROW;
+constexpr int RING = GS_RING, AHEAD = GS_AHEAD;
 constexpr int BIAS_OFF = RING * TILE_BYTES;
 constexpr int BIAS_MAX = 2048;         // bias columns a block can stage
 constexpr int LDS_BYTES = BIAS_OFF + BIAS_MAX * 4;
@@ -74,8 +63,6 @@ struct AsArgs {
   int total_items;       // kslices * per-slice items (grid may be smaller: persistent blocks)
 };
 
-__device__ __forceinline__ float as_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
 template <typename AT>
 __device__ __forceinline__ bf16x8 load_a_frag(const AT* p);
 template <>
@@ -90,24 +77,6 @@ __device__ __forceinline__ bf16x8 load_a_frag<float>(const float* p) {
   v[0] = (bf16_t)a.x; v[1] = (bf16_t)a.y; v[2] = (bf16_t)a.z; v[3] = (bf16_t)a.w;
   v[4] = (bf16_t)b.x; v[5] = (bf16_t)b.y; v[6] = (bf16_t)b.z; v[7] = (bf16_t)b.w;
   return v;
-}
-
-// s_waitcnt vmcnt(n) needs an immediate: dispatch over the even counts that can occur.
-// lgkmcnt(0) rides along so this wave's LDS writes/reads are complete before the barrier.
-__device__ __forceinline__ void wait_vm(int n) {
-  switch (n) {
-    case 20: asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory"); break;
-    case 18: asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory"); break;
-    case 16: asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); break;
-    case 14: asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)" ::: "memory"); break;
-    case 12: asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory"); break;
-    case 10: asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory"); break;
-    case 8: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;
-    case 6: asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); break;
-  }
 }
 
 // FULL: K == 512, every unrolled load / MFMA is unpredicated.  A run-time predicate (even a
@@ -141,20 +110,16 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
   if (t0 >= t1) {  // empty column range (ns is rounded up to a multiple of 8)
     if (IS_ARGMAX && lane < 32 && m0 + lane < p.M) {
       const int64_t o = (int64_t)(m0 + lane) * p.ns + ns;
-      p.pmax[o] = -INFINITY; p.pidx[o] = 0x7fffffff; p.psum[o] = 0.f;
+      gs_stat_empty(p.pmax, p.pidx, p.psum, o);
       if (HAS_LAB && p.plab) p.plab[o] = -INFINITY;
     }
     continue;
   }
   // every wave must be done reading the ring (and the bias) of the previous item
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  care_wait_vm<0>();
   __builtin_amdgcn_s_barrier();
-  if constexpr (MODE == STREAM_COLLECT) {  // candidate staging count (see collect); ordered by the first tile's barrier
-    if (tid == 0) {
-      const unsigned cb = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem + BIAS_OFF;
-      const int zero = 0;
-      asm volatile("ds_write_b32 %0, %1" :: "v"(cb), "v"(zero) : "memory");
-    }
+  if constexpr (MODE == STREAM_COLLECT) {  // candidate staging count (see collect)
+    if (tid == 0) gs_cand_reset(gs_lds_addr(smem) + BIAS_OFF);
   }
 
   const AT* Ap = reinterpret_cast<const AT*>(p.A) + slice * 512;
@@ -174,7 +139,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
   const unsigned char* wrow[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
-    wrow[i] = reinterpret_cast<const unsigned char*>(Wp + (int64_t)(wave * 4 + i) * p.ldw) + ((lane ^ (wave * 4 + i)) << 4);
+    wrow[i] = reinterpret_cast<const unsigned char*>(Wp + (int64_t)(wave * 4 + i) * p.ldw) + gs_src_chunk<true>(lane, wave * 4 + i);
   const int64_t wtile = (int64_t)TILE_N * p.ldw * 2;  // bytes between consecutive tiles
   auto stage = [&](int tile, int slot) {
     if (CARE_AS_DBG & 4) return;
@@ -182,12 +147,10 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = wave * 4 + i;
-      if (FULL || (lane ^ row) * 16 < kbytes) {
+      if (FULL || gs_src_chunk<true>(lane, row) < kbytes) {
         const unsigned char* g = wrow[i] + (int64_t)tile * wtile;
         if (!whole) g -= (int64_t)max(tile * TILE_N + row - (p.N - 1), 0) * p.ldw * 2;  // clamp to the last W row
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                         (__attribute__((address_space(3))) void*)(smem + slot * TILE_BYTES + row * 1024),
-                                         16, 0, 0);
+        gs_dma_row(g, smem + slot * TILE_BYTES + row * GS_ROW);
       }
     }
   };
@@ -235,12 +198,12 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
   // Returns the number of VM store instructions issued when that number is exact (2), else -1.
   auto store_tile = [&](int tile, float4 bv) -> int {
     const int cbase = tile * TILE_N;
-    const bool second = cbase >= p.n_split;
-    unsigned char* C = reinterpret_cast<unsigned char*>(second ? p.C1 : p.C0) + (int64_t)slice * p.slab_stride * 4;
-    const int64_t ld = second ? p.ldc1 : p.ldc0;
-    const bool isb = (second ? p.c1_bf16 : p.c0_bf16) != 0;
+    const gs_dest d = GS_DEST_OF(p, cbase, (int64_t)slice * p.slab_stride * 4);  // split-K: the slice's slab
+    unsigned char* C = d.C;
+    const int64_t ld = d.ld;
+    const bool isb = d.isb;
     const int col = cbase + fg * 4;
-    const int cc = col - (second ? p.n_split : 0);
+    const int cc = col - d.cshift;
     const bool vec = (m0 + 32 <= p.M) && (cbase + TILE_N <= p.N) && (ld % 4 == 0);
     if (CARE_AS_DBG & 1) { asm volatile("" :: "v"(acc[0]), "v"(acc[1])); return 0; }
 #pragma unroll
@@ -251,7 +214,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
         for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.0f);
       } else if (p.act == CARE_ACT_GELU) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = as_gelu(v[j]);
+        for (int j = 0; j < 4; ++j) v[j] = care_gelu(v[j]);
       }
       const int row = m0 + mt * 16 + fr;
       const int64_t o = (int64_t)row * ld + cc;
@@ -282,8 +245,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
   if constexpr (IS_ARGMAX) {
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      // finite sentinel, not -inf: an update with a masked (-inf) logit then gives exp(-inf) = 0, not NaN
-      rm[i] = -1e30f; rs[i] = 0.f; ri[i] = 0x7fffffff; rref[i] = -1e30f;
+      rm[i] = GS_STAT_MIN; rs[i] = 0.f; ri[i] = GS_STAT_NOIDX; rref[i] = GS_STAT_MIN;
       const int row = min(m0 + (i >> 2) * 16 + fg * 4 + (i & 3), p.M - 1);
       if constexpr (HAS_LAB) { rl[i] = -INFINITY; lab[i] = p.labels ? p.labels[row] : -1; }
     }
@@ -298,21 +260,11 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
       cth[i] = row < p.M ? p.bias[row] : INFINITY;
     }
   }
-  // Candidates are staged in the block's LDS bias area (idle in this mode): [0] = count, then
-  // (value, row-in-panel << 24 | column) pairs, flushed to the global lists once per work item.  A
-  // global atomic with return inside the tile loop is a full memory round trip that also drains the
-  // W tiles in flight, and about every second tile of a wave holds a candidate (417 us per launch
-  // against 257 us for the statistics pass); LDS atomics do not touch vmcnt (asm: through C++ hipcc
-  // would put a vmcnt(0) in front of them, possible alias with the LDS-DMA).
-  constexpr int LCAP = (BIAS_MAX * 4 - 8) / 8;
-  const unsigned lbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem + BIAS_OFF;
-  auto append_global = [&](int row, float v0, int c0) {
-    const int pos = atomicAdd(&p.pidx[row], 1);
-    if (pos < p.act) {
-      p.pmax[(int64_t)row * p.act + pos] = v0;
-      reinterpret_cast<int32_t*>(p.C1)[(int64_t)row * p.act + pos] = c0;
-    }
-  };
+  // Candidates are staged in the block's LDS bias area (idle in this mode; gemm_stream.h); the lists arrive in
+  // idle argument fields, see AsArgs
+  constexpr int LCAP = gs_cand_lcap(BIAS_MAX * 4);
+  const unsigned lbase = gs_lds_addr(smem) + BIAS_OFF;
+  const gs_cand_lists lists{p.pidx, p.pmax, reinterpret_cast<int32_t*>(p.C1), p.act};
   auto collect = [&](const f32x4 (&av)[2], int tile) {
     const int c0 = tile * TILE_N + fr;
     // ONE wave-uniform test per tile: a divergent branch per logit costs more than the MFMAs
@@ -325,33 +277,9 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
         const float v0 = av[i >> 2][i & 3];
         if (c0 < p.N && v0 >= cth[IS_COLLECT ? i : 0]) {
           const int rloc = wave * 32 + (i >> 2) * 16 + fg * 4 + (i & 3);
-          int pos;
-          const int one = 1;
-          asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(pos) : "v"(lbase), "v"(one) : "memory");
-          if (pos < LCAP) {
-            const unsigned a = lbase + 8 + (unsigned)pos * 8;
-            const int packed = (rloc << 24) | c0;
-            asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" :: "v"(a), "v"(v0), "v"(packed) : "memory");
-          } else {
-            append_global(m0 - wave * 32 + rloc, v0, c0);  // staging area full
-          }
+          gs_cand_push(lists, lbase, LCAP, m0 - wave * 32, rloc, v0, c0);
         }
       }
-    }
-  };
-  // flush of the staged candidates: after the tile loop of the item, all 256 threads
-  typedef int i32x2 __attribute__((ext_vector_type(2)));
-  auto collect_flush = [&]() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    int n;
-    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(n) : "v"(lbase) : "memory");
-    n = min(n, LCAP);
-    for (int e = tid; e < n; e += 256) {
-      i32x2 pr;
-      const unsigned a = lbase + 8 + (unsigned)e * 8;
-      asm volatile("ds_read2_b32 %0, %1 offset1:1\n\ts_waitcnt lgkmcnt(0)" : "=v"(pr) : "v"(a) : "memory");
-      append_global(m0 - wave * 32 + (int)((unsigned)pr[1] >> 24), __builtin_bit_cast(float, pr[0]), pr[1] & 0xffffff);
     }
   };
 
@@ -378,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
   auto argmax_ref = [&](const f32x4 (&av)[2], bool first) {
     if (first) {
 #pragma unroll
-      for (int i = 0; i < 8; ++i) rref[i] = fmaxf(av[i >> 2][i & 3], -1e30f);
+      for (int i = 0; i < 8; ++i) rref[i] = fmaxf(av[i >> 2][i & 3], GS_STAT_MIN);
       return;
     }
     float far = rm[0] - rref[0];
@@ -457,14 +385,8 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
   // ---- bias slice of this block's column range -> LDS, issued BEHIND the prologue DMAs and the A
   // loads so that all three latencies overlap (iteration 0 drains everything anyway); read back
   // with an asm ds_read, see below
-  if (MODE == STREAM_STORE && biasp) {
-    float* sb = reinterpret_cast<float*>(smem + BIAS_OFF);
-    const int nb = min((t1 - t0) * TILE_N, p.N - col0);
-    for (int i = tid; i < ((nb + 3) & ~3); i += 256) sb[i] = i < nb ? biasp[col0 + i] : 0.f;
-  }
-
-  // stage W tile `tile` into ring slot `slot`: wave w copies rows 4w..4w+3, one 1-KiB row per
-  // LDS-DMA instruction; lane = chunk slot, source chunk = slot ^ (row & 15).  4 VM ops / wave.
+  if (MODE == STREAM_STORE && biasp)
+    gs_bias_stage(reinterpret_cast<float*>(smem + BIAS_OFF), biasp, col0, min((t1 - t0) * TILE_N, p.N - col0), tid, 256);
 
   // VM operations this wave issued in each of the last AHEAD iterations, oldest first:
   // DMA count and store count (-1 = unknown: guarded scalar stores -> fall back to vmcnt(0)).
@@ -487,18 +409,13 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
       younger += hist_st[i] + (i > 0 ? hist_dma[i] : 0);
     }
     // iteration 0 drains everything (A fragments + prologue tiles were issued together)
-    wait_vm(exact && it > 0 ? younger : 0);
+    care_wait_vm_even<0>(exact && it > 0 ? younger : 0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
 
-    // bias of this lane's 4 columns: an asm ds_read (hipcc would put a vmcnt(0) drain in front
-    // of a C++ LDS read because the in-flight LDS-DMA might alias it)
+    // bias of this lane's 4 columns
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (MODE == STREAM_STORE && biasp) {
-      const unsigned base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
-      const unsigned addr = base + (unsigned)(BIAS_OFF + ((t * TILE_N - col0) + fg * 4) * 4);
-      asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(bv) : "v"(addr) : "memory");
-    }
+    if (MODE == STREAM_STORE && biasp) gs_bias_read(bv, gs_lds_addr(smem) + (unsigned)(BIAS_OFF + ((t * TILE_N - col0) + fg * 4) * 4));
 
     // ---- refill the ring slot consumed in the previous iteration
     int n_dma = 0;
@@ -529,25 +446,18 @@ __global__ __launch_bounds__(256, 2) void gemm_as_kernel(AsArgs p) {
     hist_st[AHEAD - 1] = n_st;
   }
 
-  if constexpr (IS_COLLECT) collect_flush();
+  if constexpr (IS_COLLECT) gs_cand_flush(lists, lbase, LCAP, m0 - wave * 32, tid, 256);
   if constexpr (IS_ARGMAX) {
     if constexpr (!HAS_LAB) argmax_update(accp, t1 - 1, t1 - t0 == 1);  // the last tile's statistics
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      // the sum relative to the true maximum (rows that saw no logit: rm = rref = -1e30, s = 0)
       float m = rm[i], lv = HAS_LAB ? rl[HAS_LAB ? i : 0] : 0.f;
-      float s = rs[i] > 0.f ? rs[i] * __expf(rref[IS_ARGMAX ? i : 0] - rm[i]) : 0.f;
-      if (!(s < 3.0e38f)) s = 1.0f;  // the sum overflowed (a > 88 jump inside one tile): it is its largest term
+      float s = gs_stat_close(rm[i], rs[i], rref[IS_ARGMAX ? i : 0]);
       int id = ri[i];
 #pragma unroll
-      for (int o = 1; o < 16; o <<= 1) {
+      for (int o = 1; o < 16; o <<= 1) {  // the 16 lanes (column residues) of a row
         if constexpr (HAS_LAB) lv = fmaxf(lv, __shfl_xor(lv, o, 64));
-        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-        const int oi = __shfl_xor(id, o, 64);
-        const float mn = fmaxf(m, om);
-        s = s * __expf(m - mn) + os * __expf(om - mn);
-        if (om > m || (om == m && oi < id)) id = oi;
-        m = mn;
+        gs_stat_merge(m, s, id, o);
       }
       const int row = m0 + (i >> 2) * 16 + fg * 4 + (i & 3);
       if (fr == 0 && row < p.M) {
@@ -614,12 +524,6 @@ int plan_stream(AsArgs& p, bool has_bias) {
 
 }  // namespace
 
-// the 256-row-panel store kernel for large row counts (csrc/gemm_store32.hip)
-extern "C" int care_store32_applies(int M, int N, int K, int a_dtype, int n_split, int has_bias_cols);
-extern "C" int care_store32_launch(const void* A, int64_t lda, const void* W, const float* bias, void* C0, int64_t ldc0,
-                                   int c0_bf16, void* C1, int64_t ldc1, int c1_bf16, int n_split, int M, int N, int act,
-                                   void* stream);
-
 extern "C" int care_gemm_bf16(const void* A, int64_t lda, int a_dtype, const void* W, const float* bias, void* C0,
                               int64_t ldc0, int c0_dtype, void* C1, int64_t ldc1, int c1_dtype, int n_split, int M,
                               int N, int K, int act, void* stream) {
@@ -658,16 +562,6 @@ extern "C" int care_argmax_parts_bf16(int M, int N) {
   if (M <= 0 || N <= 0) return CARE_EINVAL;
   return pick_ns((M + 127) / 128, (N + TILE_N - 1) / TILE_N);
 }
-
-// the 256-row-panel kernels for large row counts (csrc/gemm_vocab.hip)
-extern "C" int care_vocab32_applies(int M, int N, int K, int a_dtype, int has_labels);
-extern "C" int care_vocab32_launch(const void* A, int64_t lda, const void* W, float* pmax, int32_t* pidx, float* psum,
-                                   int M, int N, int ns, void* stream);
-extern "C" int care_collect32_launch(const void* A, int64_t lda, const void* W, const float* thr, int32_t* cnt, float* cval,
-                                     int32_t* cidx, int cap, int M, int N, int ns, void* stream);
-extern "C" int care_vocab32_ranges(int M, int N, int min_parts);
-extern "C" int care_vocab32_launch_tiles(const void* A, int64_t lda, const void* W, float* pmax, int32_t* pidx, float* psum,
-                                         float* tile_max, int M, int N, int ns, void* stream);
 
 // column ranges of the `_min` statistics pass (beam search): on the 256-row kernel its own rule (whole launch rounds)
 static bool min_uses_v32(int M, int N, int K, int a_dtype, int min_parts) {

@@ -46,15 +46,6 @@ struct LnArgs {
   int w_packed;  // W is in the K-step-major DMA order of care_pack_ln_weight (version-2 kernels only)
 };
 
-template <int N>
-__device__ __forceinline__ void ln_wait_vm() {
-  if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-  else if constexpr (N == 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
 // AF32: A is fp32.  RG: row groups of 64 rows (BM = 64 * RG, 4 * RG waves).
 template <bool AF32, int RG>
 __global__ __launch_bounds__(256 * RG, RG == 1 ? 1 : 2) void gemm_ln_kernel(LnArgs p) {
@@ -139,7 +130,7 @@ __global__ __launch_bounds__(256 * RG, RG == 1 ? 1 : 2) void gemm_ln_kernel(LnAr
 
   for (int kt = 0; kt < nk; ++kt) {
     // stage kt must have landed; stage kt+1 (NPW younger DMA instructions) may stay in flight
-    if (kt + 1 < nk) ln_wait_vm<NPW>(); else ln_wait_vm<0>();
+    if (kt + 1 < nk) care_wait_vmcnt<NPW>(); else care_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (kt + 2 < nk) stage(kt + 2, (kt + 2) % 3);  // the slot every wave finished reading last iteration
@@ -318,23 +309,17 @@ __device__ __forceinline__ f32x4 ln2_mfma(const bf16x8& b, const bf16x8& a, cons
   }
 }
 
-template <int N>
-__device__ __forceinline__ void ln2_wait_vm() {
-  static_assert(N >= 0 && N <= 63, "vmcnt immediate");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // wait until all but `younger` stages (PER DMA instructions each) of this wave's stream have landed
 template <int PER, int MAXY>
 __device__ __forceinline__ void ln2_wait_stages(int younger) {
   static_assert(MAXY * PER <= 63, "vmcnt range");
-  if constexpr (MAXY >= 6) { if (younger >= 6) { ln2_wait_vm<6 * PER>(); return; } }
-  if constexpr (MAXY >= 5) { if (younger == 5) { ln2_wait_vm<5 * PER>(); return; } }
-  if constexpr (MAXY >= 4) { if (younger == 4) { ln2_wait_vm<4 * PER>(); return; } }
-  if constexpr (MAXY >= 3) { if (younger == 3) { ln2_wait_vm<3 * PER>(); return; } }
-  if constexpr (MAXY >= 2) { if (younger == 2) { ln2_wait_vm<2 * PER>(); return; } }
-  if constexpr (MAXY >= 1) { if (younger == 1) { ln2_wait_vm<PER>(); return; } }
-  ln2_wait_vm<0>();
+  if constexpr (MAXY >= 6) { if (younger >= 6) { care_wait_vmcnt<6 * PER>(); return; } }
+  if constexpr (MAXY >= 5) { if (younger == 5) { care_wait_vmcnt<5 * PER>(); return; } }
+  if constexpr (MAXY >= 4) { if (younger == 4) { care_wait_vmcnt<4 * PER>(); return; } }
+  if constexpr (MAXY >= 3) { if (younger == 3) { care_wait_vmcnt<3 * PER>(); return; } }
+  if constexpr (MAXY >= 2) { if (younger == 2) { care_wait_vmcnt<2 * PER>(); return; } }
+  if constexpr (MAXY >= 1) { if (younger == 1) { care_wait_vmcnt<PER>(); return; } }
+  care_wait_vmcnt<0>();
 }
 
 // EPI: which optional epilogue operand exists - 0: none (the Embedder), 1: the residual (decoder
@@ -501,13 +486,13 @@ __global__ __launch_bounds__(256 * RG, RG) void gemm_ln2_kernel(LnArgs p) {
     for (int s = 0; s < NSW; ++s)
 #pragma unroll
       for (int i = 0; i < NWI; ++i) dma_w(min(s, nk - 1), s, i);
-    ln2_wait_vm<(NSW - 1) * NWI>();
+    care_wait_vmcnt<(NSW - 1) * NWI>();
   } else {
 #pragma unroll 1
     for (int s = 0; s < NSA - 1; ++s)   // macro stages 0 .. NSA - 2; NSA - 1 follows during macro stage 0
 #pragma unroll
       for (int i = 0; i < NAI; ++i) dma_a(min(s, nmac - 1), s, i);
-    ln2_wait_vm<(NSA - 2) * NAI>();
+    care_wait_vmcnt<(NSA - 2) * NAI>();
   }
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
@@ -540,8 +525,8 @@ __global__ __launch_bounds__(256 * RG, RG) void gemm_ln2_kernel(LnArgs p) {
     __builtin_amdgcn_sched_barrier(0);
     if (more) {
       // my stream's stage kt + 1 has landed (its younger instructions stay in flight); my reads of stage kt are done
-      if (w_loader) ln2_wait_vm<(NSW - 2) * NWI>();
-      else if (a_edge) ln2_wait_vm<AE ? 0 : REP == 1 ? (NSA - 3) * NAI + (KSUB - 1) * NAS : (NSA - 2) * NAI>();  // all of macro stage mac - 1 + NSA is out by now when REP > 1
+      if (w_loader) care_wait_vmcnt<(NSW - 2) * NWI>();
+      else if (a_edge) care_wait_vmcnt<AE ? 0 : REP == 1 ? (NSA - 3) * NAI + (KSUB - 1) * NAS : (NSA - 2) * NAI>();  // all of macro stage mac - 1 + NSA is out by now when REP > 1
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
@@ -902,7 +887,7 @@ __global__ __launch_bounds__(768) void gemm_ln3_kernel(LnArgs p) {
       ++issued;
     };
     while (issued < min(WS_NSW - 1, total)) issue();
-    if (issued > 1) ln2_wait_vm<16>(); else ln2_wait_vm<0>();
+    if (issued > 1) care_wait_vmcnt<16>(); else care_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // B_start: stage 0 has landed
     int kt = 0;
 #pragma unroll 1
@@ -912,7 +897,7 @@ __global__ __launch_bounds__(768) void gemm_ln3_kernel(LnArgs p) {
       if (issued < min(g + WS_NSW, total)) issue();
       stamp(g, 1);
       if (g > 0 && kt == 0) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }  // the previous block's E1, E2
-      if (issued > g + 2) ln2_wait_vm<16>(); else ln2_wait_vm<0>();  // stage g + 1 has landed
+      if (issued > g + 2) care_wait_vmcnt<16>(); else care_wait_vmcnt<0>();  // stage g + 1 has landed
       stamp(g, 2);
       __builtin_amdgcn_s_barrier();  // B_g
       stamp(g, 3);
@@ -1206,14 +1191,14 @@ __global__ __launch_bounds__(768) void gemm_ln3s_kernel(LnArgs p) {
       ikt = ikt + 1 == nk ? 0 : ikt + 1;
     };
     issue(0);
-    ln2_wait_vm<0>();
+    care_wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();  // B_start
     int kt = 0;
 #pragma unroll 1
     for (int g = 0; g < total; ++g) {
       if (g + 1 < total) issue(g + 1);  // into the slot stage g - 1 left at B_g-1 (also while the LayerNorm runs)
       if (g > 0 && kt == 0) { __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); __builtin_amdgcn_s_barrier(); }
-      ln2_wait_vm<0>();
+      care_wait_vmcnt<0>();
       __builtin_amdgcn_s_barrier();  // B_g
       kt = kt + 1 == nk ? 0 : kt + 1;
     }

@@ -1,10 +1,9 @@
 // gemm_store32.hip - C = act(A W^T + bias) for bf16 A [M, 512], bf16 W [N, 512] at large row counts:
 // the QKV, Wq and FFN1 projections of a decode step (Attention.py:53-67, SubLayers.py:129-141).
 //
-// Same structure as csrc/gemm_vocab.hip (see there for the ablation that motivates it: with 128-row
-// panels the L2 -> LDS stream of W bounds the A-stationary kernel before any arithmetic):
-//   * a workgroup is 8 waves x 32 rows = a 256-row panel with its A fragments resident in registers;
-//   * W tiles of 32 output columns x 512 k through a 4-slot LDS ring (LDS-DMA, three in flight), one
+// The scheme of csrc/gemm_stream.h on the panels of csrc/gemm_vocab.hip (see there for the ablation that motivates
+// them: with 128-row panels the L2 -> LDS stream of W bounds the A-stationary kernel before any arithmetic):
+//   * a workgroup is 8 waves x 32 rows = a 256-row panel, W tiles are 32 output columns x 512 k, one
 //     barrier per tile; the bias slice of the block's column range is staged in LDS once;
 //   * v_mfma_f32_32x32x16_bf16 with swapped operands; the W rows of a tile are permuted over the MFMA
 //     rows when the tile is STAGED (LDS row n takes column 16 ((n >> 2) & 1) + 4 (n >> 3) + (n & 3)), so
@@ -23,28 +22,31 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "care_common.h"
+#include "gemm_stream.h"
+
+#ifndef CARE_S32_DBG
+#define CARE_S32_DBG 0  // ablation builds: 1 no stores, 2 no bias reads, 4 no activation / conversion either, 8 lane-linear stores, 64 stamps
+#endif
+#if CARE_S32_DBG & 64  // tools (tools/variant_lib.py, tools/s32_ts.py): workgroup 0 stamps s_memtime per wave and tile
+CARE_STAMPS(s32, 8)
+#define S32_STAMP(it, k) CARE_STAMP(s32, 8, it, k)
+#else
+#define S32_STAMP(it, k) do { } while (0)
+#endif
 
 namespace {
 
-constexpr int ST_N = 32;
-constexpr int ST_BYTES = ST_N * 1024;
-constexpr int S_RING = 4, S_AHEAD = 3;
-constexpr int S_BIAS_OFF = S_RING * ST_BYTES;
+constexpr int ST_N = GS_N32;
+constexpr int S_BIAS_OFF = GS_RING * GS_TILE32;
 constexpr int S_BIAS_MAX = 4096;         // bias columns a block can stage
 constexpr int S_LDS = S_BIAS_OFF + S_BIAS_MAX * 4;
-constexpr int S_ROWS = 256;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int S_ROWS = GS_ROWS256;
 
 #ifndef CARE_S32_ST_NT
 #define CARE_S32_ST_NT 0  // non-temporal output stores (ablation)
 #endif
 #ifndef CARE_S32_QUAD
 #define CARE_S32_QUAD 1  // fp32 tiles: transpose the pieces inside lane quads before storing (0: one row per lane)
-#endif
-#ifndef CARE_S32_DBG
-#define CARE_S32_DBG 0  // ablation builds: 1 no stores, 2 no bias reads, 4 no activation / conversion either, 8 lane-linear stores, 64 stamps
 #endif
 
 struct SArgs {
@@ -56,17 +58,8 @@ struct SArgs {
   int n_split, M, N, act, ns, panels, total_items;
 };
 
-__device__ __forceinline__ float s_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
 // GELU is a template parameter: erff inlined behind a run-time test in every epilogue piece made the kernel 6872
 // instructions (55 KB) against 2658 without it - the relu / plain launches of the headline pass carried it along.
-#if CARE_S32_DBG & 64  // tools (tools/variant_lib.py, tools/s32_ts.py): workgroup 0 stamps s_memtime per wave and tile
-__device__ unsigned long long s32_stamps[8 * 64 * 4];
-#define S32_STAMP(it, k) do { if (blockIdx.x == 0 && (it) < 64 && lane == 0) s32_stamps[(wave * 64 + (it)) * 4 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define S32_STAMP(it, k) do { } while (0)
-#endif
-
 template <int BDEPTH, int ACT>  // ACT: CARE_ACT_NONE / RELU / GELU (a run-time test per value was a v_max + v_cndmask pair on every output)
 __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -83,46 +76,37 @@ __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
     const int m0 = panel * S_ROWS + wave * 32;
     const int row = m0 + r;
     // every wave is done with the ring and the bias slice of the previous item
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    care_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 
-    // ---- W tile -> ring slot: wave w copies LDS rows 4w .. 4w + 3; LDS row n holds output column
-    // perm(n) of the tile, lane = chunk slot, source chunk = slot ^ (n & 15)
+    // ---- W tile -> ring slot: wave w copies LDS rows 4w .. 4w + 3; LDS row n holds output column perm(n) of the tile
     unsigned wlane[4];
     int wcol[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int n = wave * 4 + i;
-      wlane[i] = (unsigned)((lane ^ (n & 15)) << 4);
+      wlane[i] = (unsigned)gs_src_chunk(lane, n);
       wcol[i] = 16 * ((n >> 2) & 1) + 4 * (n >> 3) + (n & 3);
     }
     auto stage = [&](int tile, int slot) {
       tile = min(tile, t1 - 1);  // past the end: the last tile again, into a slot nobody will read
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(reinterpret_cast<const unsigned char*>(p.W) +
-                                                            (int64_t)(tile * ST_N + wcol[i]) * 1024 + wlane[i]),
-            (__attribute__((address_space(3))) void*)(smem + slot * ST_BYTES + (wave * 4 + i) * 1024), 16, 0, 0);
+        gs_dma_row(reinterpret_cast<const unsigned char*>(p.W) + (int64_t)(tile * ST_N + wcol[i]) * GS_ROW + wlane[i],
+                   smem + slot * GS_TILE32 + (wave * 4 + i) * GS_ROW);
     };
 #pragma unroll
-    for (int i = 0; i < S_AHEAD; ++i) stage(t0 + i, i);
+    for (int i = 0; i < GS_AHEAD; ++i) stage(t0 + i, i);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- activations of this wave's 32 rows, whole K, resident
     bf16x8 a[32];
-    const bf16_t* arow = p.A + (int64_t)min(row, p.M - 1) * p.lda + h * 8;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) a[ks] = *reinterpret_cast<const bf16x8*>(arow + ks * 16);
+    gs_load_a32(a, p.A, p.lda, row, p.M, h);
     __builtin_amdgcn_sched_barrier(0);
 
     // ---- bias slice of the range -> LDS (behind the DMAs and the A loads: one combined latency)
     const int col0 = t0 * ST_N;
-    if (p.bias) {
-      float* sb = reinterpret_cast<float*>(smem + S_BIAS_OFF);
-      const int nb = (t1 - t0) * ST_N;
-      for (int i = tid; i < nb; i += 512) sb[i] = p.bias[col0 + i];
-    }
+    if (p.bias) gs_bias_stage(reinterpret_cast<float*>(smem + S_BIAS_OFF), p.bias, col0, (t1 - t0) * ST_N, tid, 512);
 
     // The destination is a property of the TILE (wave-uniform): a range may straddle n_split, a 32-column
     // tile cannot (n_split % 32 == 0).  VM store instructions per tile: 2 (bf16) or 4 (fp32), none for a
@@ -130,19 +114,19 @@ __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
     const bool wave_rows = m0 < p.M;
     int st_hist0 = 0, st_hist1 = 0, st_hist2 = 0;  // stores issued in the iterations it - 1, it - 2, it - 3
 
-    const int bswz = r * 1024;
-    auto boff = [&](int ks) { return bswz + ((((2 * ks + h) ^ (r & 15)) & 15) << 4) + ((2 * ks) >> 4) * 256; };
-    const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
+    const int bswz = r * GS_ROW;
+    auto boff = [&](int ks) { return bswz + gs_frag32(r, h, ks); };
+    const unsigned lds0 = gs_lds_addr(smem);
 
-    f32x16 accA, accB;
+    care_f32x16 accA, accB;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { accA[i] = 0.f; accB[i] = 0.f; }
 
     // epilogue piece g (0..3) of a finished tile: columns 16 h + 4 g .. + 3 of this lane's row
     // (accumulator registers 4 g .. 4 g + 3 hold output columns 16 h + 4 g + (0..3) after the staging permutation)
-    auto out_piece = [&](const f32x16& ap, int tile, int g, float (&v)[16]) {
+    auto out_piece = [&](const care_f32x16& ap, int tile, int g, float (&v)[16]) {
       float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (p.bias && !(CARE_S32_DBG & 2)) {  // asm read: hipcc would drain the in-flight DMAs in front of a C++ LDS read here
+      if (p.bias && !(CARE_S32_DBG & 2)) {  // gs_bias_read, written out: through the helper hipcc moves the zeroing of bv in the RELU / GELU kernels
         const unsigned addr = lds0 + (unsigned)(S_BIAS_OFF + ((tile * ST_N - col0) + 16 * h + 4 * g) * 4);
         asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(bv) : "v"(addr) : "memory");
       }
@@ -150,16 +134,16 @@ __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
       v[4 * g + 2] = ap[4 * g + 2] + bv.z; v[4 * g + 3] = ap[4 * g + 3] + bv.w;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if constexpr (ACT == CARE_ACT_GELU) v[4 * g + j] = s_gelu(v[4 * g + j]);
+        if constexpr (ACT == CARE_ACT_GELU) v[4 * g + j] = care_gelu(v[4 * g + j]);
         else if constexpr (ACT == CARE_ACT_RELU) v[4 * g + j] = fmaxf(v[4 * g + j], 0.0f);
       }
     };
     auto out_store = [&](int tile, const float (&v)[16]) -> int {
-      const bool second = tile * ST_N >= p.n_split;
-      unsigned char* C = reinterpret_cast<unsigned char*>(second ? p.C1 : p.C0);
-      const int64_t ld = second ? p.ldc1 : p.ldc0;
-      const bool isb = (second ? p.c1_bf16 : p.c0_bf16) != 0;
-      const int cshift = second ? p.n_split : 0;
+      const gs_dest d = GS_DEST_OF(p, tile * ST_N, 0);
+      unsigned char* C = d.C;
+      const int64_t ld = d.ld;
+      const bool isb = d.isb;
+      const int cshift = d.cshift;
       if (!isb && CARE_S32_QUAD && !(CARE_S32_DBG & 9)) {  // wave-uniform: every lane takes part in the exchange
         // fp32 tile: a lane holds 64 contiguous bytes of ITS row, so a store instruction is 64 separate 16-byte
         // pieces.  A 4 x 4 transpose of the 16-byte pieces inside every quad of lanes (rows 4q .. 4q + 3, DPP
@@ -241,32 +225,23 @@ __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
       // the tile has landed when at most the DMAs of the two younger tiles (8) and the stores issued since
       // its own DMA are outstanding: its DMA went out three iterations ago (or in the prologue) AHEAD of
       // that iteration's stores
-      switch (8 + st_hist0 + st_hist1 + st_hist2) {
-        case 8: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;
-        case 10: asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory"); break;
-        case 12: asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)" ::: "memory"); break;
-        case 14: asm volatile("s_waitcnt vmcnt(14) lgkmcnt(0)" ::: "memory"); break;
-        case 16: asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); break;
-        case 18: asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory"); break;
-        case 20: asm volatile("s_waitcnt vmcnt(20) lgkmcnt(0)" ::: "memory"); break;
-        default: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;  // odd counts (ragged last panel): wait for more
-      }
+      care_wait_vm_even<8>(8 + st_hist0 + st_hist1 + st_hist2);  // odd counts (ragged last panel): wait for more
     };
 
-    auto tile_body = [&](int t, auto with_prev, f32x16& ac, f32x16& ap) {
+    auto tile_body = [&](int t, auto with_prev, care_f32x16& ac, care_f32x16& ap) {
       constexpr bool PREV = decltype(with_prev)::value;
       const int it = t - t0;
       S32_STAMP(it, 0);
-      if constexpr (!PREV) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // also the A fragments and the bias slice
+      if constexpr (!PREV) care_wait_vm<0>();  // also the A fragments and the bias slice
       else wait_tile();
       S32_STAMP(it, 1);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       S32_STAMP(it, 2);
-      stage(t + S_AHEAD, (it + S_AHEAD) % S_RING);
+      stage(t + GS_AHEAD, (it + GS_AHEAD) % GS_RING);
       __builtin_amdgcn_sched_barrier(0);
 
-      const unsigned char* sb = smem + (it % S_RING) * ST_BYTES;
+      const unsigned char* sb = smem + (it % GS_RING) * GS_TILE32;
       bf16x8 fb[BDEPTH];
 #pragma unroll
       for (int ks = 0; ks < BDEPTH; ++ks) fb[ks] = *reinterpret_cast<const bf16x8*>(sb + boff(ks));
@@ -275,7 +250,7 @@ __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
       for (int ks = 0; ks < 32; ++ks) {
         const bf16x8 b = fb[ks % BDEPTH];
         if (ks + BDEPTH < 32) fb[ks % BDEPTH] = *reinterpret_cast<const bf16x8*>(sb + boff(ks + BDEPTH));
-        if (ks == 0) ac = care_mfma_32x32x16_h16(b, a[0], f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        if (ks == 0) ac = care_mfma_32x32x16_h16(b, a[0], care_f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         else ac = care_mfma_32x32x16_h16(b, a[ks], ac, 0, 0, 0);
         if constexpr (PREV) {
           if (ks % 6 == 5 && ks / 6 < 4) out_piece(ap, t - 1, ks / 6, v);   // pieces after k-steps 5, 11, 17, 23
@@ -293,7 +268,7 @@ __global__ __launch_bounds__(512, 2) void gemm_store32_kernel(SArgs p) {
       tile_body(t, std::true_type{}, accB, accA);
       tile_body(t + 1, std::true_type{}, accA, accB);
     }
-    auto last_out = [&](const f32x16& al) {
+    auto last_out = [&](const care_f32x16& al) {
       float v[16];
 #pragma unroll
       for (int g = 0; g < 4; ++g) out_piece(al, t1 - 1, g, v);
@@ -322,33 +297,18 @@ extern "C" int care_store32_launch(const void* A, int64_t lda, const void* W, co
   p.A = reinterpret_cast<const bf16_t*>(A); p.lda = lda; p.W = reinterpret_cast<const bf16_t*>(W); p.bias = bias;
   p.C0 = C0; p.ldc0 = ldc0; p.c0_bf16 = c0_bf16; p.C1 = C1; p.ldc1 = ldc1; p.c1_bf16 = c1_bf16;
   p.n_split = n_split; p.M = M; p.N = N; p.act = act;
-  p.panels = (M + S_ROWS - 1) / S_ROWS;
+  const int panels = (M + S_ROWS - 1) / S_ROWS;
   // column ranges per panel: enough work items for one workgroup per CU (256), whole tiles per range; the
   // bias slice of a range must fit its LDS staging area
   const int tiles = N / ST_N;
   int ns = 1;
-  while ((p.panels * ns < 256 && ns * 2 <= tiles) || ((tiles + ns - 1) / ns) * ST_N > S_BIAS_MAX) ns *= 2;
+  while ((panels * ns < 256 && ns * 2 <= tiles) || ((tiles + ns - 1) / ns) * ST_N > S_BIAS_MAX) ns *= 2;
   if (((tiles + ns - 1) / ns) * ST_N > S_BIAS_MAX) return CARE_ESHAPE;
   p.ns = ns;
-  p.total_items = p.panels * ns;
   // 16-byte stores: destinations and leading dimensions must allow them
   const int e0 = c0_bf16 ? 8 : 4, e1 = c1_bf16 ? 8 : 4;
   if ((ldc0 % e0) || !care_aligned16(C0) || (n_split < N && ((ldc1 % e1) || !care_aligned16(C1)))) return CARE_EALIGN;
-  const int blocks = p.total_items < 256 ? p.total_items : 256;
-  auto go = [&](auto actc) -> int {
-    constexpr int A = decltype(actc)::value;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (const int e = care_allow_dynamic_lds(reinterpret_cast<const void*>(&gemm_store32_kernel<4, A>), S_LDS, lds_ok)) return e;
-    hipLaunchKernelGGL((gemm_store32_kernel<4, A>), dim3(blocks), dim3(512), S_LDS, (hipStream_t)stream, p);
-    return 0;
-  };
-  if (const int e = act == CARE_ACT_GELU ? go(std::integral_constant<int, CARE_ACT_GELU>{})
-                  : act == CARE_ACT_RELU ? go(std::integral_constant<int, CARE_ACT_RELU>{})
-                                         : go(std::integral_constant<int, CARE_ACT_NONE>{}))
-    return e;
-  return care_launch_status();
+  return act == CARE_ACT_GELU ? gs_launch256<&gemm_store32_kernel<4, CARE_ACT_GELU>>(p, S_LDS, stream)
+       : act == CARE_ACT_RELU ? gs_launch256<&gemm_store32_kernel<4, CARE_ACT_RELU>>(p, S_LDS, stream)
+                              : gs_launch256<&gemm_store32_kernel<4, CARE_ACT_NONE>>(p, S_LDS, stream);
 }
-
-#if CARE_S32_DBG & 64
-extern "C" int care_s32_stamps(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(s32_stamps), sizeof(s32_stamps)); }
-#endif

@@ -51,6 +51,16 @@
 
 #include "care_common.h"
 
+#ifndef CARE_TILE_DBG
+#define CARE_TILE_DBG 0  // tools (tools/variant_lib.py, tools/tile_ts.py): 64 - workgroup 0 stamps s_memtime per wave and K step
+#endif
+#if CARE_TILE_DBG & 64
+CARE_STAMPS(tile, 16)
+#define TILE_STAMP(kt, k) CARE_STAMP(tile, 16, kt, k)
+#else
+#define TILE_STAMP(kt, k) do { } while (0)
+#endif
+
 namespace {
 
 struct TArgs {
@@ -101,13 +111,6 @@ __device__ __forceinline__ void tile_of_block(const int tiles_m, const int tiles
   const int rows = min(group, tiles_m - b * group);
   tm = b * group + o % rows;
   tn = o / rows;
-}
-
-__device__ __forceinline__ float t_gelu(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
-
-template <int N_>
-__device__ __forceinline__ void t_wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N_) : "memory");
 }
 
 // The epilogue of a wave's (16 MT) x 64 outputs:
@@ -168,7 +171,7 @@ __device__ __forceinline__ void tile_epilogue(const TArgs& p, f32x4 (&acc)[MT][4
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           float x = (p.amax_a ? acc[m][n][j] * alpha : acc[m][n][j]) + bv[4 * n + j];
-          if constexpr (GELU) x = t_gelu(x);
+          if constexpr (GELU) x = care_gelu(x);
           else x = p.act == CARE_ACT_RELU ? fmaxf(x, 0.0f) : x;
           v[4 * n + j] = x;
         }
@@ -395,15 +398,6 @@ __device__ __forceinline__ void tile_epilogue(const TArgs& p, f32x4 (&acc)[MT][4
 // twice the stages in the same LDS, i.e. more K steps of prefetch for the same bytes in use).  Swizzle of a 64-byte
 // row's four 16-byte chunks: chunk ^= G[(row >> 2) & 3], G = {0, 3, 2, 1} - the 16 lanes of every ds_read_b128 lane
 // group ({0-3, 12-15, 20-27}, ...) then fall on 16 different 16-byte slots of the 256-byte bank row.
-#ifndef CARE_TILE_DBG
-#define CARE_TILE_DBG 0  // tools (tools/variant_lib.py, tools/tile_ts.py): 64 - workgroup 0 stamps s_memtime per wave and K step
-#endif
-#if CARE_TILE_DBG & 64
-__device__ unsigned long long tile_stamps[16 * 64 * 4];
-#define TILE_STAMP(kt, k) do { if (blockIdx.x == 0 && blockIdx.y == 0 && (kt) < 64 && lane == 0 && wave < 16) tile_stamps[(wave * 64 + (kt)) * 4 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define TILE_STAMP(kt, k) do { } while (0)
-#endif
 
 template <int WGM, int WGN, int WTM, int STAGES, int EPI, bool F16 = false, int BK = 64, bool GELU = false>
 __global__ __launch_bounds__(64 * WGM * WGN) void gemm_tile_kernel(TArgs p) {
@@ -485,8 +479,8 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_tile_kernel(TArgs p) {
     __builtin_amdgcn_sched_barrier(0);  // the MFMAs of step kt - 1 (and the waits on their fragments) stay above the barrier
     // step kt has landed when at most the STAGES - 2 younger steps of this wave are outstanding
     TILE_STAMP(kt, 0);
-    if (kt + STAGES - 2 < nk) t_wait_vm<(STAGES - 2) * P>();
-    else t_wait_vm<0>();
+    if (kt + STAGES - 2 < nk) care_wait_vm<(STAGES - 2) * P>();
+    else care_wait_vm<0>();
     TILE_STAMP(kt, 1);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
@@ -901,7 +895,3 @@ extern "C" int care_gemm_tile_argmax(const void* A, int64_t lda, const void* W, 
   p.labels = labels; p.plab = plab;
   return labels ? dispatch<EPI_ARGMAX_LAB>(p, (hipStream_t)stream) : dispatch<EPI_ARGMAX>(p, (hipStream_t)stream);
 }
-
-#if CARE_TILE_DBG & 64
-extern "C" int care_tile_stamps(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(tile_stamps), sizeof(tile_stamps)); }
-#endif

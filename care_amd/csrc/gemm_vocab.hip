@@ -9,9 +9,9 @@
 // i.e. 128 flop per streamed byte caps the kernel at 2 PFLOP/s before any arithmetic happens.  MFMA
 // issue (32 x 16x16x32 per 16-column tile), 13-instruction-per-logit statistics over 8 rows per lane
 // and the fragment reads then ADD to that instead of hiding in it (114 + 62 + 76 us).  Here:
-//   * a workgroup is 8 waves x 32 rows = a 256-row panel: W is streamed half as often (256 flop/B);
-//   * W tiles are 32 columns x 512 k (32 KiB) through a 4-slot LDS ring, three in flight, one barrier
-//     per tile = per 1024 MFMA cycles of every wave;
+// the scheme of csrc/gemm_stream.h (resident A, ring of W tiles, counted waits) with
+//   * a workgroup of 8 waves x 32 rows = a 256-row panel: W is streamed half as often (256 flop/B);
+//   * W tiles of 32 columns x 512 k (32 KiB), one barrier per tile = per 1024 MFMA cycles of every wave;
 //   * v_mfma_f32_32x32x16_bf16 with the operands swapped (D = (X W^T)^T): half the MFMA instructions
 //     per flop, and a lane ends up with 16 columns of ONE row, so the running statistics of a row are
 //     four registers in one lane (maximum, its column, sum of exponentials, the sum's lazy reference)
@@ -30,18 +30,24 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "care_common.h"
+#include "gemm_stream.h"
+
+#ifndef CARE_V32_DBG
+#define CARE_V32_DBG 0  // ablation: 2 no MFMA, 16 no statistics, 32 no fragment reads
+#endif
+#if CARE_V32_DBG & 64  // tools (tools/variant_lib.py, tools/v32_ts.py): workgroup 0 stamps s_memtime per wave and tile
+CARE_STAMPS(v32, 8)
+#define V32_STAMP(it, k) CARE_STAMP(v32, 8, it, k)
+#else
+#define V32_STAMP(it, k) do { } while (0)
+#endif
 
 namespace {
 
-constexpr int VT_N = 32;                 // columns per W tile
-constexpr int VT_BYTES = VT_N * 1024;    // K = 512 bf16
-constexpr int V_RING = 4, V_AHEAD = 3;
-constexpr int V_LDS = V_RING * VT_BYTES;
-constexpr int V_ROWS = 256;              // rows per workgroup (8 waves x 32)
+constexpr int VT_N = GS_N32;             // columns per W tile
+constexpr int V_LDS = GS_RING * GS_TILE32;
+constexpr int V_ROWS = GS_ROWS256;       // rows per workgroup (8 waves x 32)
 constexpr float V_LOG2E = 1.4426950408889634f;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct VArgs {
   const bf16_t* A; int64_t lda;
@@ -57,20 +63,10 @@ struct VArgs {
 
 enum { V_ARGMAX = 0, V_COLLECT = 1 };
 constexpr int V_STAGE = 8192;                  // collect: LDS staging of the candidates of one work item
-constexpr int V_LCAP = (V_STAGE - 8) / 8;
+constexpr int V_LCAP = gs_cand_lcap(V_STAGE);
 
 #ifndef V32_STAGGER
 #define V32_STAGGER 1  // the two waves of a SIMD take MFMAs / statistics in opposite order (0: both multiply first)
-#endif
-#ifndef CARE_V32_DBG
-#define CARE_V32_DBG 0  // ablation: 2 no MFMA, 16 no statistics, 32 no fragment reads
-#endif
-
-#if CARE_V32_DBG & 64  // tools (tools/variant_lib.py, tools/v32_ts.py): workgroup 0 stamps s_memtime per wave and tile
-__device__ unsigned long long v32_stamps[8 * 64 * 4];
-#define V32_STAMP(it, k) do { if (blockIdx.x == 0 && (it) < 64 && lane == 0) v32_stamps[(wave * 64 + (it)) * 4 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define V32_STAMP(it, k) do { } while (0)
 #endif
 
 template <int BDEPTH, int MODE>
@@ -97,76 +93,56 @@ __global__ __launch_bounds__(512, 2) void vocab_argmax32_kernel(VArgs p) {
     const int row = m0 + r;
     // ranges past the last tile (ns does not divide the tile count evenly) hold nothing
     if (!COLLECT && h == 0 && row < p.M)
-      for (int range = max(ra, (tiles_total + tpb - 1) / tpb); range < rb; ++range) {
-        const int64_t o = (int64_t)row * p.ns + range;
-        p.pmax[o] = -INFINITY; p.pidx[o] = 0x7fffffff; p.psum[o] = 0.f;
-      }
+      for (int range = max(ra, (tiles_total + tpb - 1) / tpb); range < rb; ++range)
+        gs_stat_empty(p.pmax, p.pidx, p.psum, (int64_t)row * p.ns + range);
     if (t0 >= t1) continue;
     // every wave is done reading the ring of the previous run
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    care_wait_vm<0>();
     __builtin_amdgcn_s_barrier();
-    // collect: candidates are staged in LDS behind the ring - [0] = count, then (value, row-in-panel << 24 | column)
-    // pairs - and flushed to the global lists once per run (a global atomic with return inside the tile loop
-    // is a memory round trip that also drains the W tiles in flight); LDS atomics via asm (no vmcnt involvement)
-    const unsigned lbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem + V_LDS;
-    if (COLLECT && tid == 0) {  // ordered before the first append by the first tile's barrier
-      const int zero = 0;
-      asm volatile("ds_write_b32 %0, %1" ::"v"(lbase), "v"(zero) : "memory");
-    }
+    // collect: the candidates of a run are staged in LDS behind the ring (gemm_stream.h)
+    const unsigned lbase = gs_lds_addr(smem) + V_LDS;
+    const gs_cand_lists lists{p.cnt, p.cval, p.cidx, p.cap};
+    if (COLLECT && tid == 0) gs_cand_reset(lbase);
     const float thr = COLLECT ? (row < p.M ? p.thr[row] : INFINITY) : 0.f;
 
-    // ---- W tile -> ring slot: wave w copies rows 4w .. 4w + 3 of the 32 (one 1-KiB row per DMA
-    // instruction); lane = chunk slot, source chunk = slot ^ (row & 15): conflict-free ds_read_b128
+    // ---- W tile -> ring slot: wave w copies rows 4w .. 4w + 3 of the 32
     const unsigned char* wrow[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) wrow[i] = reinterpret_cast<const unsigned char*>(p.W) + ((lane ^ ((wave * 4 + i) & 15)) << 4);
+    for (int i = 0; i < 4; ++i) wrow[i] = reinterpret_cast<const unsigned char*>(p.W) + gs_src_chunk(lane, wave * 4 + i);
     auto stage = [&](int tile, int slot) {
       tile = min(tile, t1 - 1);  // past the end: the last tile again, into a slot nobody will read
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int n = min(tile * VT_N + wave * 4 + i, p.N - 1);  // ragged last tile: clamp to the last W row
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(wrow[i] + (int64_t)n * 1024),
-                                         (__attribute__((address_space(3))) void*)(smem + slot * VT_BYTES + (wave * 4 + i) * 1024),
-                                         16, 0, 0);
+        gs_dma_row(wrow[i] + (int64_t)n * GS_ROW, smem + slot * GS_TILE32 + (wave * 4 + i) * GS_ROW);
       }
     };
 #pragma unroll
-    for (int i = 0; i < V_AHEAD; ++i) stage(t0 + i, i);
+    for (int i = 0; i < GS_AHEAD; ++i) stage(t0 + i, i);
     __builtin_amdgcn_sched_barrier(0);
 
-    // ---- activations of this wave's 32 rows, whole K, resident: fragment ks = X[row][16 ks + 8 h + (0..7)]
+    // ---- activations of this wave's 32 rows, whole K, resident
     bf16x8 a[32];
-    const bf16_t* arow = p.A + (int64_t)min(row, p.M - 1) * p.lda + h * 8;
-#pragma unroll
-    for (int ks = 0; ks < 32; ++ks) a[ks] = *reinterpret_cast<const bf16x8*>(arow + ks * 16);
+    gs_load_a32(a, p.A, p.lda, row, p.M, h);
     __builtin_amdgcn_sched_barrier(0);
 
-    // per-lane W fragment offset: row r of the tile, chunk (2 ks + h) ^ (r & 15); the ks part is an
-    // XOR of the low four chunk bits with (2 ks & 15) and an add of 256 per 8 k-steps
-    const int bswz = r * 1024;
-    auto boff = [&](int ks) { return bswz + ((((2 * ks + h) ^ (r & 15)) & 15) << 4) + ((2 * ks) >> 4) * 256; };
+    const int bswz = r * GS_ROW;
+    auto boff = [&](int ks) { return bswz + gs_frag32(r, h, ks); };
 
-    float rm = -1e30f, rs = 0.f, rref = -1e30f;
-    float rref2 = -1e30f * V_LOG2E;  // rref * log2(e): one fma + one exp2 per logit (MFMA and VALU time ADD on a SIMD, §4.1c)
-    int ri = 0x7fffffff;
-    f32x16 acc, accp;
+    float rm = GS_STAT_MIN, rs = 0.f, rref = GS_STAT_MIN;
+    float rref2 = GS_STAT_MIN * V_LOG2E;  // rref * log2(e): one fma + one exp2 per logit (MFMA and VALU time ADD on a SIMD, §4.1c)
+    int ri = GS_STAT_NOIDX;
+    care_f32x16 acc, accp;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { acc[i] = 0.f; accp[i] = 0.f; }
 
     // column of accumulator register i of this lane inside a tile
-    auto col_in_tile = [&](int i) { return (i & 3) + 8 * (i >> 2) + 4 * h; };
+    auto col_in_tile = [&](int i) { return gs_col32(i, h); };
     // statistics of one finished tile held in accp: pieces woven between the MFMAs of the next tile
     float tmax = -INFINITY;
     auto stat_piece = [&](int i) {  // logit i of 16
       tmax = fmaxf(tmax, accp[i]);
       if (!COLLECT) rs += __builtin_amdgcn_exp2f(fmaf(accp[i], V_LOG2E, -rref2));
-    };
-    auto append_global = [&](int grow, float v, int c) {
-      const int pos = atomicAdd(&p.cnt[grow], 1);
-      if (pos < p.cap) {
-        p.cval[(int64_t)grow * p.cap + pos] = v;
-        p.cidx[(int64_t)grow * p.cap + pos] = c;
-      }
     };
     auto stat_open = [&](int tile, bool first) {
       if (tile * VT_N + VT_N > p.N) {  // ragged last tile of the vocabulary: columns past N never win nor count
@@ -174,7 +150,7 @@ __global__ __launch_bounds__(512, 2) void vocab_argmax32_kernel(VArgs p) {
         for (int i = 0; i < 16; ++i)
           if (tile * VT_N + col_in_tile(i) >= p.N) accp[i] = -INFINITY;
       }
-      if (first && !COLLECT) { rref = fmaxf(accp[0], -1e30f); rref2 = rref * V_LOG2E; }
+      if (first && !COLLECT) { rref = fmaxf(accp[0], GS_STAT_MIN); rref2 = rref * V_LOG2E; }
       tmax = -INFINITY;
     };
     auto stat_close = [&](int tile) {
@@ -185,18 +161,7 @@ __global__ __launch_bounds__(512, 2) void vocab_argmax32_kernel(VArgs p) {
           for (int i = 0; i < 16; ++i) {
             const float v = accp[i];
             const int c = tile * VT_N + col_in_tile(i);
-            if (v >= thr && c < p.N) {
-              int pos;
-              const int one = 1;
-              asm volatile("ds_add_rtn_u32 %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=v"(pos) : "v"(lbase), "v"(one) : "memory");
-              if (pos < V_LCAP) {
-                const unsigned a = lbase + 8 + (unsigned)pos * 8;
-                const int packed = ((wave * 32 + r) << 24) | c;
-                asm volatile("ds_write2_b32 %0, %1, %2 offset1:1" ::"v"(a), "v"(v), "v"(packed) : "memory");
-              } else {
-                append_global(row, v, c);  // staging area full
-              }
-            }
+            if (v >= thr && c < p.N) gs_cand_push(lists, lbase, V_LCAP, m0 - wave * 32, wave * 32 + r, v, c);
           }
         }
         return;
@@ -227,24 +192,24 @@ __global__ __launch_bounds__(512, 2) void vocab_argmax32_kernel(VArgs p) {
       // tile t has landed; the two younger tiles (4 DMA instructions each) stay in flight.  Iteration 0
       // drains everything: the A fragments were issued behind the prologue DMAs.
       V32_STAMP(it, 0);
-      if constexpr (!decltype(with_stats)::value) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      else if (COLLECT || !p.tile_max) asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory");
+      if constexpr (!decltype(with_stats)::value) care_wait_vm<0>();
+      else if (COLLECT || !p.tile_max) care_wait_vm<8>();
       else {  // + the tile_max stores issued since this tile's DMA went out (iterations it - 3 .. it - 1 that had statistics)
         switch (min(it - 1, 3)) {
-          case 0: asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)" ::: "memory"); break;
-          case 1: asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory"); break;
-          case 2: asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory"); break;
-          default: asm volatile("s_waitcnt vmcnt(11) lgkmcnt(0)" ::: "memory"); break;
+          case 0: care_wait_vm<8>(); break;
+          case 1: care_wait_vm<9>(); break;
+          case 2: care_wait_vm<10>(); break;
+          default: care_wait_vm<11>(); break;
         }
       }
       V32_STAMP(it, 1);
       __builtin_amdgcn_s_barrier();
       __builtin_amdgcn_sched_barrier(0);
       V32_STAMP(it, 2);
-      stage(t + V_AHEAD, (it + V_AHEAD) % V_RING);  // the slot every wave finished reading last iteration
+      stage(t + GS_AHEAD, (it + GS_AHEAD) % GS_RING);  // the slot every wave finished reading last iteration
       __builtin_amdgcn_sched_barrier(0);
 
-      const unsigned char* sb = smem + (it % V_RING) * VT_BYTES;
+      const unsigned char* sb = smem + (it % GS_RING) * GS_TILE32;
       // A wave cannot issue VALU work in the shadow of its OWN MFMAs (tools/micro/mfma_valu_overlap.hip: they add), so
       // the statistics of tile t - 1 (~180 VALU instructions) only overlap the matrix pipe if the OTHER wave of the SIMD
       // is multiplying meanwhile.  The per-tile barrier starts all eight waves together: left alone both waves of a SIMD
@@ -289,19 +254,14 @@ __global__ __launch_bounds__(512, 2) void vocab_argmax32_kernel(VArgs p) {
     // the statistics of a finished range: merge the two lanes of a row (columns 4 h + ...), write (max, argmax,
     // sum relative to the max), start over
     auto close_range = [&](int range) {
-      float m = rm, sx = rs > 0.f ? rs * __expf(rref - rm) : 0.f;
-      if (!(sx < 3.0e38f)) sx = 1.0f;  // the sum overflowed (a > 88 jump inside one tile): it is its largest term
+      float m = rm, sx = gs_stat_close(rm, rs, rref);
       int id = ri;
-      const float om = __shfl_xor(m, 32, 64), os = __shfl_xor(sx, 32, 64);
-      const int oi = __shfl_xor(id, 32, 64);
-      const float mn = fmaxf(m, om);
-      sx = sx * __expf(m - mn) + os * __expf(om - mn);
-      if (om > m || (om == m && oi < id)) id = oi;
+      gs_stat_merge(m, sx, id, 32);
       if (h == 0 && row < p.M) {
         const int64_t o = (int64_t)row * p.ns + range;
-        p.pmax[o] = mn; p.pidx[o] = id; p.psum[o] = sx;
+        p.pmax[o] = m; p.pidx[o] = id; p.psum[o] = sx;
       }
-      rm = -1e30f; rs = 0.f; rref = -1e30f; rref2 = -1e30f * V_LOG2E; ri = 0x7fffffff;
+      rm = GS_STAT_MIN; rs = 0.f; rref = GS_STAT_MIN; rref2 = GS_STAT_MIN * V_LOG2E; ri = GS_STAT_NOIDX;
     };
     tile_body(t0, std::false_type{});
 #pragma unroll 1
@@ -316,19 +276,8 @@ __global__ __launch_bounds__(512, 2) void vocab_argmax32_kernel(VArgs p) {
       for (int i = 0; i < 16; ++i) stat_piece(i);
       stat_close(t1 - 1);
     }
-    if constexpr (COLLECT) {  // flush the staged candidates: all 512 threads
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      typedef int i32x2 __attribute__((ext_vector_type(2)));
-      int n;
-      asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(n) : "v"(lbase) : "memory");
-      n = min(n, V_LCAP);
-      for (int e = tid; e < n; e += 512) {
-        i32x2 pr;
-        const unsigned a = lbase + 8 + (unsigned)e * 8;
-        asm volatile("ds_read2_b32 %0, %1 offset1:1\n\ts_waitcnt lgkmcnt(0)" : "=v"(pr) : "v"(a) : "memory");
-        append_global(panel * V_ROWS + (int)((unsigned)pr[1] >> 24), __builtin_bit_cast(float, pr[0]), pr[1] & 0xffffff);
-      }
+    if constexpr (COLLECT) {
+      gs_cand_flush(lists, lbase, V_LCAP, panel * V_ROWS, tid, 512);
     } else {
       close_range((t1 - 1) / tpb);
     }
@@ -343,8 +292,6 @@ extern "C" int care_vocab32_applies(int M, int N, int K, int a_dtype, int has_la
   return K == 512 && a_dtype == CARE_BF16 && !has_labels && M >= min_rows && N >= 4 * VT_N;
 }
 
-extern "C" int care_vocab32_launch_tiles(const void* A, int64_t lda, const void* W, float* pmax, int32_t* pidx, float* psum,
-                                         float* tile_max, int M, int N, int ns, void* stream);
 extern "C" int care_vocab32_launch(const void* A, int64_t lda, const void* W, float* pmax, int32_t* pidx, float* psum,
                                    int M, int N, int ns, void* stream) {
   return care_vocab32_launch_tiles(A, lda, W, pmax, pidx, psum, nullptr, M, N, ns, stream);
@@ -354,13 +301,7 @@ extern "C" int care_vocab32_launch_tiles(const void* A, int64_t lda, const void*
   VArgs p{};
   p.A = reinterpret_cast<const bf16_t*>(A); p.lda = lda; p.W = reinterpret_cast<const bf16_t*>(W);
   p.pmax = pmax; p.pidx = pidx; p.psum = psum; p.M = M; p.N = N; p.ns = ns; p.tile_max = tile_max;
-  p.panels = (M + V_ROWS - 1) / V_ROWS;
-  p.total_items = p.panels * ns;
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (const int e = care_allow_dynamic_lds(reinterpret_cast<const void*>(&vocab_argmax32_kernel<6, V_ARGMAX>), V_LDS, lds_ok)) return e;
-  const int blocks = p.total_items < 256 ? p.total_items : 256;  // one workgroup per CU (128 KiB of LDS), persistent
-  hipLaunchKernelGGL((vocab_argmax32_kernel<6, V_ARGMAX>), dim3(blocks), dim3(512), V_LDS, (hipStream_t)stream, p);
-  return care_launch_status();
+  return gs_launch256<&vocab_argmax32_kernel<6, V_ARGMAX>>(p, V_LDS, stream);
 }
 
 // Second pass of the fused beam selection (care_gemm_collect_bf16) on the same 256-row panels.
@@ -369,14 +310,7 @@ extern "C" int care_collect32_launch(const void* A, int64_t lda, const void* W, 
   VArgs p{};
   p.A = reinterpret_cast<const bf16_t*>(A); p.lda = lda; p.W = reinterpret_cast<const bf16_t*>(W);
   p.thr = thr; p.cnt = cnt; p.cval = cval; p.cidx = cidx; p.cap = cap; p.M = M; p.N = N; p.ns = ns;
-  p.panels = (M + V_ROWS - 1) / V_ROWS;
-  p.total_items = p.panels * ns;
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (const int e = care_allow_dynamic_lds(reinterpret_cast<const void*>(&vocab_argmax32_kernel<6, V_COLLECT>), V_LDS + V_STAGE, lds_ok))
-    return e;
-  const int blocks = p.total_items < 256 ? p.total_items : 256;
-  hipLaunchKernelGGL((vocab_argmax32_kernel<6, V_COLLECT>), dim3(blocks), dim3(512), V_LDS + V_STAGE, (hipStream_t)stream, p);
-  return care_launch_status();
+  return gs_launch256<&vocab_argmax32_kernel<6, V_COLLECT>>(p, V_LDS + V_STAGE, stream);
 }
 
 // Column ranges for the 256-row panels: whole launch rounds over the 256 CUs, each work item paying ~3 tile times of
@@ -394,7 +328,3 @@ extern "C" int care_vocab32_ranges(int M, int N, int min_parts) {
   }
   return best;
 }
-
-#if CARE_V32_DBG & 64
-extern "C" int care_v32_stamps(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(v32_stamps), sizeof(v32_stamps)); }
-#endif

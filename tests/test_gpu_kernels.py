@@ -876,6 +876,32 @@ def test_fused_beam_selection_equals_logits_plus_beam_select(M, V, bm):
         assert (got_v[over] - ref_v[over]).abs().max().item() < 1e-3
 
 
+@pytest.mark.parametrize("M,V", [(130, 3000), (8192 + 40, 700)])
+def test_gemm_collect_with_a_full_staging_area(M, V):
+    """care_gemm_collect_bf16 with a threshold every logit reaches: each row's list must end up with all V columns,
+    once each, and their logits.  A work item stages at most 1023 candidates in LDS and appends the rest straight to
+    the global lists - the branch the fused-selection tests (about ten candidates a row) never take.  130 x 3000 runs
+    on the 128-row panels of csrc/gemm_as.hip (two panels, the second with 2 live rows; >= 2048 candidates per item of
+    the first), 8232 x 700 on the 256-row panels of csrc/gemm_vocab.hip (22 tiles, the last one ragged at 28 columns;
+    >= 8192 per item)."""
+    K = 512
+    A = _rand(M, K, seed=71).to(torch.bfloat16)
+    W = _rand(V, K, seed=72, scale=1 / math.sqrt(K)).to(torch.bfloat16)
+    thr = torch.full((M,), -1e30, device=DEV)
+    cnt = torch.zeros(M, device=DEV, dtype=torch.int32)
+    cap = V
+    cval = torch.full((M, cap), float("nan"), device=DEV)
+    cidx = torch.full((M, cap), -1, device=DEV, dtype=torch.int32)
+    _call("care_gemm_collect_bf16", _p(A), K, 1, _p(W), _p(thr), _p(cnt), _p(cval), _p(cidx), cap, M, V, K)
+    torch.cuda.synchronize()
+    assert torch.equal(cnt, torch.full_like(cnt, V))
+    cols, order = cidx.long().sort(1)
+    assert torch.equal(cols, torch.arange(V, device=DEV).expand(M, V))
+    ref = A.double() @ W.double().t()
+    err = (cval.gather(1, order).double() - ref).abs().max().item()
+    assert err < 3e-3, err
+
+
 @pytest.mark.parametrize("M,V,K,bm", [(5, 10547, 512, 5), (300, 10547, 512, 5), (640, 10547, 512, 4), (130, 700, 512, 2), (64, 10547, 1024, 5),
                                       (2560, 10547, 512, 5), (777, 9000, 768, 3), (33, 128, 512, 5), (300, 10547, 512, 8), (64, 3000, 512, 6)])
 def test_beam_selection_from_group_maxima_equals_logits_plus_beam_select(M, V, K, bm):

@@ -400,6 +400,28 @@ def test_gemm_ln(M, K, a_f32, packed, variant):
     assert torch.equal(only.view(torch.int16), outb.view(torch.int16))
 
 
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("M,V", [(130, 3000), (8192 + 40, 700)])
+def test_gemm_collect_with_a_full_staging_area(M, V, variant):
+    """care_gemm_collect_bf16 with a threshold every logit reaches: all V columns of every row, once each, with their
+    logits.  A work item stages at most 1023 candidates in LDS; the rest go straight to the global lists.  130 x 3000:
+    the 128-row panels of csrc/gemm_as.hip; 8232 x 700: the 256-row panels of csrc/gemm_vocab.hip, ragged last tile."""
+    K = 512
+    h16, call = _h16(variant), _caller(variant)
+    A = _rand(M, K, seed=71).to(h16)
+    W = _rand(V, K, seed=72, scale=1 / math.sqrt(K)).to(h16)
+    thr = torch.full((M,), -1e30, device=DEV)
+    cnt = torch.zeros(M, device=DEV, dtype=torch.int32)
+    cval = torch.full((M, V), float("nan"), device=DEV)
+    cidx = torch.full((M, V), -1, device=DEV, dtype=torch.int32)
+    call("care_gemm_collect_bf16", _p(A), K, 1, _p(W), _p(thr), _p(cnt), _p(cval), _p(cidx), V, M, V, K)
+    torch.cuda.synchronize()
+    assert torch.equal(cnt, torch.full_like(cnt, V))
+    cols, order = cidx.long().sort(1)
+    assert torch.equal(cols, torch.arange(V, device=DEV).expand(M, V))
+    _assert_f32(cval.gather(1, order), A.double() @ W.double().t(), "gemm_collect, full staging area")
+
+
 # ------------------------------------------------------------------------------------------------ row kernels
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("d", [512, 1024])
