@@ -19,6 +19,9 @@ and the data set resident in HBM, every training / validation batch built on the
 and the test epoch - per-video scores, the predictions and the caption analysis `ave_length` / `novel` / `unique` / `usage`
 against the training captions, all kept on the device (care_amd/corpusstats.py, care_amd/testepoch.py):
     from care_amd import CorpusBank, EpochCaptions, TestEpoch
+and the consensus among a clip's sampled captions - the candidate that agrees most with the others under CIDEr-D, chosen on
+the device (care_amd/consensus.py; Translator_ARFormer.consensus_batch):
+    from care_amd import consensus_select
 """
 from .framework import get_framework  # noqa: F401
 from .translator import get_translator  # noqa: F401
@@ -33,7 +36,8 @@ from .validation import ValidationEpoch  # noqa: F401
 from .clipstore import ClipStore  # noqa: F401
 from .corpusstats import CorpusBank, EpochCaptions  # noqa: F401
 from .testepoch import TestEpoch  # noqa: F401
+from .consensus import consensus_select  # noqa: F401
 
-__all__ = ["CorpusBank", "EpochCaptions", "TestEpoch", "ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+__all__ = ["consensus_select", "CorpusBank", "EpochCaptions", "TestEpoch", "ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
            "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
            "CaptionBank", "attach_retrieval"]

@@ -122,6 +122,7 @@ SIGNATURES = {
     "care_retrieval_topk": [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P],
     "care_retrieval_gather": [_P, _I, _I, _P, _I, _P, _P],
     "care_cider_score": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "care_consensus_score": [_P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "care_reward_advantage": [_P, _P, _I, _I, _P, _P, _P],
     "care_reward_loss_fwd": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "care_reward_loss_bwd": [_P, _L, _L, _I, _I, _P, _P, _P, _P, _P, _P, _P, _L, _L, _I, _I, _P],

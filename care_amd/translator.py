@@ -132,16 +132,7 @@ class Translator_ARFormer(object):
         1, no filter: what a pseudo-label or a sequence-level objective weighs - over length ** beam_alpha.  with_logq: a
         third list, the un-normalised sum of the log-probabilities under the distribution actually drawn from (what an
         importance weight needs).  One model in eval mode on the device; there is no CPU form."""
-        from .engine_sample import check_sample_args
-        check_sample_args(n_samples, temperature, top_k, top_p)
-        if len(models) != 1:
-            raise ValueError("sample_batch draws from ONE model, got {} (ensembles are outside sampled decoding)".format(len(models)))
-        if getattr(models[0], "training", False):
-            raise ValueError("sample_batch needs the model in eval mode: call .eval() (training mode runs under autograd)")
-        feats = batch["feats"]
-        feats = list(feats[0] if isinstance(feats[0], list) else feats)
-        if not all(isinstance(f, torch.Tensor) and f.is_cuda for f in feats):
-            raise ValueError("sample_batch needs the features on the device: CPU tensors have no fallback path")
+        self._check_sample_call("sample_batch", models, batch, n_samples, temperature, top_k, top_p)
         with self._device_of(models), self._turn(models), torch.no_grad():
             engine, feats = self._engine_and_feats(models, batch)
             _, fed, length, score, score_q = engine.translate_sample(feats, n_samples, temperature, top_k, top_p, seed=seed,
@@ -160,6 +151,63 @@ class Translator_ARFormer(object):
                 q = score_q.astype(np.float64).tolist()
                 return hyps, scores, [q[i: i + n] for i in range(0, len(q), n)]
             return hyps, scores
+
+    @staticmethod
+    def _check_sample_call(who, models, batch, n_samples, temperature, top_k, top_p) -> None:
+        """The refusals of the sampled entry points (`who`: sample_batch, consensus_batch), by name, before anything runs."""
+        from .engine_sample import check_sample_args
+        check_sample_args(n_samples, temperature, top_k, top_p)
+        if len(models) != 1:
+            raise ValueError("{} draws from ONE model, got {} (ensembles are outside sampled decoding)".format(who, len(models)))
+        if getattr(models[0], "training", False):
+            raise ValueError("{} needs the model in eval mode: call .eval() (training mode runs under autograd)".format(who))
+        feats = batch["feats"]
+        feats = list(feats[0] if isinstance(feats[0], list) else feats)
+        if not all(isinstance(f, torch.Tensor) and f.is_cuda for f in feats):
+            raise ValueError("{} needs the features on the device: CPU tensors have no fallback path".format(who))
+
+    def consensus_batch(self, models: List[torch.nn.Module], batch: dict, bank, n_samples: int = 5, temperature: float = 1.0,
+                        top_k: int = 0, top_p: float = 1.0, seed: int = None, sample_ids=None, use_graph: bool = True):
+        """ONE caption per clip: of the `n_samples` captions `sample_batch` draws with these settings, the one that agrees
+        most with the clip's other draws under CIDEr-D over token ids (include/care_hip.h,
+        care_consensus_score) - a pseudo-label chosen by consensus, not by the model's own log-probability.  `bank`: a
+        care_amd.CiderBank with device tables (its corpus statistics weigh the n-grams, its `with_eos` is the convention;
+        no references of the clip are read).  The draws, their consensus scores and the winners stay on the device; the
+        winners' rows are gathered there and fetched in one copy.  Returns `(batch_hyps, batch_scores)` in
+        translate_batch's format: batch_hyps[i] = [the caption], batch_scores[i] = [the MODEL's log-probability of it over
+        length ** beam_alpha], as sample_batch reports it.  `self.last_consensus`: device tensors - `tokens` int32
+        [B, max_len - 1], `length` int32 [B] and `score` fp32 [B] of the winners, `consensus` fp32 [B, n_samples] (every
+        draw's consensus score) and `winner` int32 [B] (the draw that won; the lower among equals).  With n_samples = 1 the
+        draw itself comes back.  The refusals of sample_batch, and a `bank` that is not a CiderBank."""
+        from .consensus import MAX_CANDIDATES, consensus_select
+        from .reward import CiderBank
+        if not isinstance(bank, CiderBank):
+            raise TypeError("`bank` must be a care_amd.CiderBank, got {}".format(type(bank).__name__))
+        if bank.desc is None:
+            raise RuntimeError("this bank was built with device=None (host tables only): the consensus is scored on the MI355X")
+        self._check_sample_call("consensus_batch", models, batch, n_samples, temperature, top_k, top_p)
+        if n_samples > MAX_CANDIDATES:
+            raise ValueError("`n_samples` {} > {}: the candidates of a clip a consensus is taken among".format(n_samples, MAX_CANDIDATES))
+        with self._device_of(models), self._turn(models), torch.no_grad():
+            engine, feats = self._engine_and_feats(models, batch)
+            _, fed, length, score, _ = engine.translate_sample(feats, n_samples, temperature, top_k, top_p, seed=seed,
+                                                               use_graph=use_graph, sample_ids=sample_ids)
+            consensus, winner, winner_row, _ = consensus_select(fed, length, n_samples, bank, offset=1)
+            # the winners' rows of the pass's workspaces as ONE block of its own, [tokens | length | score's bits] a row: what
+            # last_consensus views and one copy fetches
+            T = fed.shape[1] - 1
+            rows = torch.cat([fed[:, 1:], length.view(-1, 1), score.view(torch.int32).view(-1, 1)], dim=1)
+            block = rows.index_select(0, winner_row.to(torch.int64))
+            self.last_consensus = {"tokens": block[:, :T], "length": block[:, T], "score": block[:, T + 1].view(torch.float32),
+                                   "consensus": consensus, "winner": winner}
+            event, (host,) = self._fetch([block])
+            if event is not None:
+                event.synchronize()
+            length, score = host[:, T], host[:, T + 1].view(np.float32)
+            hyps = []
+            for _ in self._token_lists(hyps, host[:, :T], length, wrap=True):
+                pass
+            return hyps, [[s] for s in self._norm(score, length).tolist()]
 
     # ------------------------------------------------------------------ launch: the device pass + one D2H copy
     _ABORTED = ("the resident decode timed out at a hand-off: its workgroups never became resident together (another "

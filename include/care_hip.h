@@ -1060,6 +1060,44 @@ int care_reward_loss_bwd(const float* logits, int64_t ld, int64_t seq_stride, in
                          float* dlogits, int64_t ldd, int64_t dseq_stride, int seq_rows, int rows, void* stream);
 
 /*
+ * Consensus captions (care_amd/consensus.py, Translator_ARFormer.consensus_batch; csrc/consensus.hip): of the n candidate
+ * captions of a clip - the samples of care_sample_logits - the one that agrees most with the others under CIDEr-D (minimum
+ * Bayes risk with the task's metric as the gain).  No references of the clip are read: the bank gives ln N and ln df only.
+ * Restated in float64 in tests/consensus_reference.py.  fp32 / double arithmetic in both libraries, no atomics, nothing
+ * synchronises, nothing is allocated.
+ *
+ * care_consensus_score: clip b owns the candidate rows b n + j, j = 0 .. n - 1, of which the first m = count[b] (clamped
+ *   into [0, n]; count NULL: m = n) are valid.  A candidate is the caption of care_cider_score: tokens[r * ld + col0 .. +
+ *   min(length[r], width)) with ONE trailing `eos` dropped unless with_eos != 0, its keys and weights w(g) = tf(g) (ln N -
+ *   ln max(1, df(g))) those of care_cider_score (df = 0 for a key that is absent from corpus_keys).  For j != i, both < m:
+ *     sim_o(j -> i) = sum_{g in j, order o} min(w_j(g), w_i(g)) w_i(g),  divided by norm_o(j) norm_o(i) when both are non-zero;
+ *     t_o(j, i)     = sim_o(j -> i) exp(-(len_j - len_i)^2 / 72);
+ *     pairs[b, j, i] = 10 (((t_1 + t_2) + t_3) + t_4) / 4;
+ *     score[b, j]    = 10 (((a_1 / (m - 1) + a_2 / (m - 1)) + a_3 / (m - 1)) + a_4 / (m - 1)) / 4,
+ *                      a_o = the sum of t_o(j, i) over i != j, i < m, in ascending i
+ *   - the CIDEr-D of candidate j with the clip's other valid candidates as its reference set; duplicates each count as a
+ *   reference; an empty candidate scores 0 and, as a reference, adds 0 and still counts in m - 1.  pairs[b, j, j] = 0, every
+ *   pairs / score entry with j >= m or i >= m is 0, and with m <= 1 every score is 0.  winner[b] = the j < m with the largest
+ *   score[b, j] AS WRITTEN (the double rounded to fp32), the lower j among equals - the first arg-max of the row the caller
+ *   reads; -1 when m == 0.  (Copies of one caption get the same terms in another order of i, so their doubles may differ in
+ *   the last bit: compared as doubles, that bit and not the index would choose among them.)  winner_row[b] = b n + winner[b],
+ *   or -1.
+ *   Every sum is in double and in ONE order - the norms in key order, sim_o by a scan in lane order (a lane per key of j, key
+ *   l + 64 q on lane l), a_o in ascending i - so a clip's bits depend on the clip alone; score and pairs are rounded once to
+ *   fp32.  pairs [clips, n, n] and winner_row [clips] are optional.
+ *   One workgroup of 256 per clip; per candidate 256 keys, 256 weights, 4 norms, 64 tokens in LDS: 4400 n + 8 bytes, 137.5 KB
+ *   at CARE_CONSENSUS_MAX_N.
+ *   NULL tokens / length / bank / score / winner, a NULL corpus_keys / corpus_lndf, clips < 0, n < 1, width < 1, col0 < 0,
+ *   ld < col0 + width, n_videos < 1 -> CARE_EINVAL; n > CARE_CONSENSUS_MAX_N, width > 64, clips n > 2^31 - 1 -> CARE_ESHAPE;
+ *   corpus_keys / corpus_lndf not 8-byte aligned -> CARE_EALIGN; before anything is launched.  clips == 0 is a no-op that
+ *   returns 0.
+ */
+#define CARE_CONSENSUS_MAX_N 32
+int care_consensus_score(const int32_t* tokens, int ld, int col0, int width, const int32_t* length, const int32_t* count,
+                         int clips, int n, int with_eos, int eos, const care_cider_bank* bank, float* score, float* pairs,
+                         int32_t* winner, int32_t* winner_row, void* stream);
+
+/*
  * Validation metrics (care_amd/capmetrics.py, care_amd/validation.py; csrc/capmetrics.hip): what the reference's validation
  * epoch reports besides METEOR (models/Wrapper.py:214-273, misc/cocoeval.py) - corpus BLEU-1..4, ROUGE-L and CIDEr - over
  * integer token ids, from sufficient statistics that stay on the device for a whole epoch.  The definitions are coco-caption's,
