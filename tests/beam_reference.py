@@ -52,6 +52,24 @@ class BeamStateRef:
         self.count = {k: 0 for k in BRANCHES}
         self.clip_count = [{k: 0 for k in BRANCHES} for _ in range(B)]
 
+    @classmethod
+    def from_arrays(cls, arrays, B, bm, need, T, V, mutant=None):
+        """A restatement that goes on from COPIES of existing tables (those of arrays(): a device state copied to the host), with
+        any row stride >= T + 1 and any number of guard rows / clips behind the B * bm rows / B clips."""
+        self = cls.__new__(cls)
+        assert mutant is None or mutant in MUTANTS
+        self.B, self.bm, self.need, self.T, self.V, self.mutant = B, bm, need, T, V, mutant
+        a = {k: np.array(v, copy=True) for k, v in arrays.items()}
+        self.tok, self.anc, self.scores = a["tok"], [a["anc0"], a["anc1"]], a["scores"]
+        self.done, self.nfin, self.fscore, self.flen, self.fhyp = a["done"], a["nfin"], a["fscore"], a["flen"], a["fhyp"]
+        self.stride, self.cap = self.tok.shape[1], self.fscore.shape[1]
+        assert self.stride >= T + 1 and self.tok.shape[0] >= B * bm and self.done.shape[0] >= B and self.cap >= 1
+        assert self.anc[0].shape == self.anc[1].shape == self.tok.shape and self.fhyp.shape == self.fscore.shape + (self.stride,)
+        assert self.tok.dtype == np.int32 and self.scores.dtype == np.float32 and self.fscore.dtype == np.float32
+        self.count = {k: 0 for k in BRANCHES}
+        self.clip_count = [{k: 0 for k in BRANCHES} for _ in range(B)]
+        return self
+
     def arrays(self):
         return dict(tok=self.tok, anc0=self.anc[0], anc1=self.anc[1], scores=self.scores, done=self.done, nfin=self.nfin,
                     fscore=self.fscore, flen=self.flen, fhyp=self.fhyp)
@@ -67,9 +85,39 @@ class BeamStateRef:
             return [True] * bm
         return [self.tok[a_old[b * bm + i, t - 1], t - 1] != EOS for i in range(bm)]
 
-    def step(self, t, cand_val, cand_idx):
-        """Step t (1 .. T) on the candidates [B*bm, bm] of every row: value (a log-probability) and column."""
+    def pool_choice(self, b, t, cand_val, cand_idx):
+        """What the selection rule keeps for clip b at step t from the candidates [B*bm, bm] of every row, slot by slot:
+        (parent[bm], token[bm], score[bm] fp32; an empty slot is (0, EOS, -1e20)), and whether the pruning edge was a tie."""
+        bm, V, row0 = self.bm, self.V, b * self.bm
+        # candidate pool: (value, flat index i*V + col); the first step looks at row 0 only, ended beams offer nothing
+        n_src = bm if (t > 1 or self.mutant == "first_all") else 1
+        live = self.live_rows(b, t)
+        pool = []
+        for i in range(n_src):
+            if not live[i] and self.mutant != "ended_stay":
+                continue
+            for j in range(bm):
+                v = np.float32(cand_val[row0 + i, j])
+                if t > 1:
+                    v = np.float32(v + self.scores[row0 + i])
+                col = int(cand_idx[row0 + i, j])
+                pool.append((v, i * V + col, i, col))
+        # the bm best: value descending, flat index ascending
+        sign = -1 if self.mutant == "tie_desc" else 1
+        pool.sort(key=lambda c: (-float(c[0]), sign * c[1]))
+        sc = [np.float32(-1e20)] * bm
+        parent, token = [0] * bm, [EOS] * bm
+        for k, (v, _, i, col) in enumerate(pool[:bm]):
+            sc[k], parent[k], token[k] = v, i, col
+        return (parent, token, sc), len(pool) > bm and pool[bm - 1][0] == pool[bm][0]
+
+    def step(self, t, cand_val=None, cand_idx=None, chosen=None):
+        """Step t (1 .. T) on the candidates [B*bm, bm] of every row: value (a log-probability) and column.  Or, with `chosen` -
+        one (parent[bm], token[bm], score[bm] fp32) per clip - on a selection made elsewhere: the pool and its sort are
+        bypassed (the entry of a frozen clip is ignored), everything after them - ancestors, tokens, scores, finished lists, the
+        endings, frozen clips, the branch counters but `boundary_tie` - is the same code."""
         assert 1 <= t <= self.T
+        assert (chosen is None) != (cand_val is None)
         bm, V, need, cap = self.bm, self.V, self.need, self.cap
         a_old, a_new, tok = self.anc[(t - 1) & 1], self.anc[t & 1], self.tok
         stop_at = need + 1 if self.mutant == "need_plus1" else need
@@ -83,28 +131,14 @@ class BeamStateRef:
                     tok[row0 + i, t] = EOS
                 self._hit(b, "frozen")
                 continue
-            # candidate pool: (value, flat index i*V + col); the first step looks at row 0 only, ended beams offer nothing
-            n_src = bm if (t > 1 or self.mutant == "first_all") else 1
-            live = self.live_rows(b, t)
-            pool = []
-            for i in range(n_src):
-                if not live[i] and self.mutant != "ended_stay":
-                    continue
-                for j in range(bm):
-                    v = np.float32(cand_val[row0 + i, j])
-                    if t > 1:
-                        v = np.float32(v + self.scores[row0 + i])
-                    col = int(cand_idx[row0 + i, j])
-                    pool.append((v, i * V + col, i, col))
-            # the bm best: value descending, flat index ascending
-            sign = -1 if self.mutant == "tie_desc" else 1
-            pool.sort(key=lambda c: (-float(c[0]), sign * c[1]))
-            if len(pool) > bm and pool[bm - 1][0] == pool[bm][0]:
-                self._hit(b, "boundary_tie")
-            sc = [np.float32(-1e20)] * bm
-            parent, token = [0] * bm, [EOS] * bm
-            for k, (v, _, i, col) in enumerate(pool[:bm]):
-                sc[k], parent[k], token[k] = v, i, col
+            if chosen is None:
+                (parent, token, sc), tie = self.pool_choice(b, t, cand_val, cand_idx)
+                if tie:
+                    self._hit(b, "boundary_tie")
+            else:
+                parent, token = [int(x) for x in chosen[b][0]], [int(x) for x in chosen[b][1]]
+                sc = [np.float32(x) for x in chosen[b][2]]
+                assert len(parent) == len(token) == len(sc) == bm and all(0 <= i < bm for i in parent)
             # rewire the ancestors, record tokens and scores
             anew = [a_old[row0 + parent[i], :t].copy() for i in range(bm)]
             for i in range(bm):

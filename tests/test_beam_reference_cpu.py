@@ -79,6 +79,28 @@ def test_scripts_reach_every_branch():
     assert all(total[k] > 0 for k in BRANCHES), total
 
 
+@pytest.mark.parametrize("ties", [False, True])
+def test_a_step_on_a_given_choice_equals_the_step_on_the_pool(ties):
+    """step(chosen = what the pool rule picks), on a restatement built from copies of the tables (from_arrays), leaves the bytes
+    of step() - after every step of every scripted search, boundary_tie apart the same branch counts."""
+    for shape in SHAPES[:7]:
+        B, bm, need, T, V = shape
+        logp = script(B, bm, T, V, SEED, ties)
+        ref, snaps = cached_run(shape, ties)
+        other = BeamStateRef(B, bm, need, T, V)
+        total = {k: 0 for k in BRANCHES}
+        for t in range(1, T + 1):
+            cv, ci = candidates(logp[t - 1], bm)
+            other = BeamStateRef.from_arrays(other.arrays(), B, bm, need, T, V)
+            other.step(t, chosen=[other.pool_choice(b, t, cv, ci)[0] for b in range(B)])
+            for k, want in snaps[t - 1].items():
+                assert np.array_equal(other.arrays()[k].view(np.int32), want.view(np.int32)), (shape, t, k)
+            for k in BRANCHES:
+                total[k] += other.count[k]
+        assert total["boundary_tie"] == 0
+        assert all(total[k] == ref.count[k] for k in BRANCHES if k != "boundary_tie"), (shape, total, ref.count)
+
+
 @pytest.mark.parametrize("mutant", MUTANTS)
 def test_a_wrong_rule_changes_what_the_device_test_compares(mutant):
     """tie-break by descending flat index / first step over all rows / ended beams left in the pool / stop at need + 1: each
