@@ -11,7 +11,8 @@ and the mean-teacher step of `--wrapper InterplayModel` (models/Wrapper.py:550-6
 and the `r` modality retrieved on device from a bank of caption embeddings (pretreatment/clip_retrieval.py; care_amd/retrieval.py):
     from care_amd import CaptionBank, attach_retrieval
 and self-critical sequence training on the CIDEr-D of sampled captions (care_amd/reward.py, care_amd/scst.py):
-    from care_amd import CiderBank, self_critical_loss, SelfCriticalStep
+    from care_amd import CiderBank, self_critical_loss, self_critical_head_loss, SelfCriticalStep
+(`self_critical_head_loss`, `SelfCriticalStep(..., fused_head=True)`: the vocabulary head inside the loss, no [N, t, V] logits)
 and the validation epoch scored on device - corpus BLEU, ROUGE-L and CIDEr over token ids (care_amd/capmetrics.py, care_amd/validation.py):
     from care_amd import MetricBank, ValidationEpoch
 and the data set resident in HBM, every training / validation batch built on the device (care_amd/clipstore.py):
@@ -29,7 +30,7 @@ from .criterion import Criterion, LanguageGeneration, NoisyOrMIL, get_criterion 
 from .optim import Adam, configure_optimizers, filter_weight_decay  # noqa: F401
 from .interplay import InterplayStep, distillation_mse, ema_update  # noqa: F401
 from .retrieval import CaptionBank, attach_retrieval  # noqa: F401
-from .reward import CiderBank, self_critical_loss  # noqa: F401
+from .reward import CiderBank, self_critical_head_loss, self_critical_loss  # noqa: F401
 from .scst import SelfCriticalStep  # noqa: F401
 from .capmetrics import MetricBank  # noqa: F401
 from .validation import ValidationEpoch  # noqa: F401
@@ -38,6 +39,6 @@ from .corpusstats import CorpusBank, EpochCaptions  # noqa: F401
 from .testepoch import TestEpoch  # noqa: F401
 from .consensus import consensus_select  # noqa: F401
 
-__all__ = ["consensus_select", "CorpusBank", "EpochCaptions", "TestEpoch", "ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "SelfCriticalStep","get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
+__all__ = ["consensus_select", "CorpusBank", "EpochCaptions", "TestEpoch", "ClipStore", "MetricBank", "ValidationEpoch", "CiderBank", "self_critical_loss", "self_critical_head_loss", "SelfCriticalStep", "get_framework", "get_translator", "get_criterion", "Criterion", "LanguageGeneration", "NoisyOrMIL",
            "Adam", "configure_optimizers", "filter_weight_decay", "InterplayStep", "distillation_mse", "ema_update",
            "CaptionBank", "attach_retrieval"]

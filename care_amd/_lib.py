@@ -106,6 +106,10 @@ SIGNATURES = {
     "care_head_grad_scale": [_P, _P, _P],
     "care_gemm_tile_split3_head_grad": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _P],
     "care_pieces_transpose": [_P, _I, _I, _I, _I, _I, _P, _P],
+    "care_head_reward_finish": [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "care_head_reward_reduce": [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P],
+    "care_head_reward_gscale": [_P, _P, _P, _P, _P],
+    "care_rows_scale": [_P, _L, _P, _P, _L, _I, _I, _P],
     "care_active_slots": [_P, _I, _P, _P, _P],
     "care_gather_rows": [_P, _L, _P, _L, _P, _I, _L, _P],
     "care_scatter_rows": [_P, _L, _P, _L, _P, _I, _L, _P],

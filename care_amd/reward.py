@@ -14,8 +14,13 @@ reward or the leave-one-out mean of a clip's other samples; `self_critical_loss`
 
 with its backward to the logits.  n_live, the upstream gradient and every reward stay on the device: nothing here waits for it.
 
-As everywhere in care_amd there is no CPU fallback: CPU tensors raise.  A `DeferredLogits` (model.set_fused_head(True)) is
-refused by name - the loss is taken over the [N, t, V] logits the fused head never materialises.
+`self_critical_head_loss` is the same loss with the vocabulary head inside (csrc/head_reward.hip): it takes
+the decoder's hidden states and the head's weight - the two halves of a `DeferredLogits` - and runs the projection, the loss
+and its backward over the live label positions only, the [N, t, V] logits and their gradient never in memory.  It needs the
+number of live positions on the host: the caller's `live`, or one 4-byte read-back.
+
+As everywhere in care_amd there is no CPU fallback: CPU tensors raise.  `self_critical_loss` itself refuses a `DeferredLogits`
+(model.set_fused_head(True)) by name - it is taken over the [N, t, V] logits the fused head never materialises.
 """
 import ctypes
 import math
@@ -29,7 +34,7 @@ from .captions import MAX_CAPTION, MAX_VOCAB, caption_rows, need_device, strip_e
 from .constants import EOS, PAD
 from .criterion import DeferredLogits, _seq_rows, _seq_rows_grad
 
-__all__ = ["CiderBank", "reward_advantage", "self_critical_loss", "pack_ngrams", "MAX_CAPTION"]
+__all__ = ["CiderBank", "reward_advantage", "self_critical_loss", "self_critical_head_loss", "pack_ngrams", "MAX_CAPTION"]
 
 ORDERS = 4
 
@@ -246,4 +251,162 @@ def self_critical_loss(logits, labels, advantages, acc: Optional[torch.Tensor] =
     labels32 = labels.to(torch.int32).contiguous()
     adv = advantages.detach().to(torch.float32).reshape(-1).contiguous()
     loss, seq_logp, totals = _WeightedLogLik.apply(logits, labels32, adv, acc)
+    return (loss, seq_logp, totals) if return_aux else loss
+
+
+class _HeadRewardLoss(torch.autograd.Function):
+    """_WeightedLogLik with the vocabulary head inside (Head.py:26-32 + the loss above), over the live label positions only:
+    hidden2d [N * tl, d], W [V, d] -> (loss, seq_logp [N], totals [2]); backward -> (dhidden [N * tl, d] with dead rows exactly
+    zero, dW [V, d]).  criterion._HeadLoss's products (csrc/gemm_tile.hip, EPI_HEAD_STATS / EPI_HEAD_GRAD with eps = 0); a row's
+    weight - its caption's advantage - is linear, so it multiplies the d-wide rows on either side of the gradient's two
+    products (care_rows_scale) and never the [R, V] side.  `live`: the number of live label positions when the host knows
+    it; None: read back from the device (4 bytes)."""
+
+    @staticmethod
+    def forward(ctx, hidden2d, W, labels32, adv, acc, live=None):
+        from . import criterion
+        from .training import _absmax_slot, _f32c
+        call, ptr = _lib.call, _lib.ptr
+        N, t = labels32.shape
+        d, V = hidden2d.shape[1], W.shape[0]
+        tl = hidden2d.shape[0] // N
+        assert hidden2d.shape[0] == N * tl and tl >= t and W.shape[1] == d, (tuple(hidden2d.shape), tuple(W.shape), (N, t))
+        h, Wc = _f32c(hidden2d), _f32c(W)
+        dev, rows = h.device, N * t
+        idx = torch.zeros(3, rows, device=dev, dtype=torch.int32)       # live row -> row of h, label position, label
+        cnt = torch.empty(2, device=dev, dtype=torch.int32)
+        call("care_head_live_rows", ptr(labels32), N, t, tl, V, ptr(idx[0]), ptr(idx[1]), ptr(idx[2]), ptr(cnt))
+        R = int(cnt[0].item()) if live is None else int(live)           # the one 4-byte read-back, unless the caller has it
+        if not 0 <= R <= rows:
+            raise ValueError("`live` = {} for {} label positions".format(R, rows))
+        cst = torch.empty(4, max(R, 1), device=dev, dtype=torch.float32)   # max, log sum exp(x - max), logp, weight per LIVE row
+        totals = torch.empty(2, device=dev, dtype=torch.float64)           # sum adv logp, n_live
+        loss = torch.empty((), device=dev, dtype=torch.float32)
+        seq_logp = torch.empty(N, device=dev, dtype=torch.float32)
+        if R > 0:   # (an all-PAD batch launches nothing with M = 0)
+            h_live = torch.empty(R, d, device=dev, dtype=torch.float32)
+            call("care_gather_rows", ptr(h), h.stride(0) * 4, ptr(h_live), d * 4, ptr(idx[0]), R, d * 4)
+            ksd, parts = criterion._ceil64(d), (V + 63) // 64
+            h_slot, w_slot = _absmax_slot(h_live), _absmax_slot(Wc)
+            a2 = torch.empty(R, 2 * ksd, device=dev, dtype=torch.float16)
+            w3 = torch.empty(V, 3 * ksd, device=dev, dtype=torch.float16)
+            call("care_split_pieces", ptr(h_live), d, R, d, 0, 1, ksd, ptr(a2), 2, h_slot.data_ptr())
+            call("care_split_pieces", ptr(Wc), Wc.stride(0), V, d, 0, 1, ksd, ptr(w3), 3, w_slot.data_ptr())
+            for a, b in criterion.head_chunks(R):
+                n = b - a
+                pf = torch.empty(4, n, parts, device=dev, dtype=torch.float32)
+                pi = torch.empty(n, parts, device=dev, dtype=torch.int32)
+                call("care_gemm_tile_split3_head_stats", ptr(a2[a:]), ptr(w3), h_slot.data_ptr(), w_slot.data_ptr(), ptr(idx[2][a:]),
+                     ptr(pf[0]), ptr(pi), ptr(pf[1]), ptr(pf[2]), ptr(pf[3]), n, V, ksd)
+                call("care_head_reward_finish", ptr(pf[0]), ptr(pf[1]), ptr(pf[2]), parts, ptr(idx[1][a:]), ptr(adv), t, V, n,
+                     ptr(cst[0][a:]), ptr(cst[1][a:]), ptr(cst[2][a:]), ptr(cst[3][a:]), tag="head_reward_finish")
+            # W's pieces are not kept for the backward: split again there from the same |max| - the same bits (as _HeadLoss)
+            ctx.save_for_backward(h_live, Wc, a2, idx, cst, h_slot, w_slot, totals)
+        call("care_head_reward_reduce", ptr(cst[2]), ptr(cst[3]), ptr(idx[1]), R, t, N, ptr(totals), ptr(loss), ptr(seq_logp), ptr(acc),
+             tag="head_reward_reduce")
+        ctx.R, ctx.h_shape, ctx.w_shape = R, tuple(hidden2d.shape), tuple(W.shape)
+        ctx.mark_non_differentiable(seq_logp, totals)
+        return loss, seq_logp, totals
+
+    @staticmethod
+    def backward(ctx, g, _gs, _gt):
+        from . import criterion
+        from .training import _absmax_slot, _strided_sum, _x3_slabs
+        call, ptr = _lib.call, _lib.ptr
+        (rows_h, d), (V, _) = ctx.h_shape, ctx.w_shape
+        R, dev = ctx.R, g.device
+        need_dh, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        zeros = lambda *shape: torch.zeros(*shape, device=dev, dtype=torch.float32)   # (a fill kernel, not a memset node)
+        if R == 0:
+            return (zeros(rows_h, d) if need_dh else None), (zeros(V, d) if need_dw else None), None, None, None, None
+        h_live, Wc, a2, idx, cst, h_slot, w_slot, totals = ctx.saved_tensors
+        g32 = g.to(torch.float32).reshape(1).contiguous()   # a device scalar: the kernels read it, the host never does
+        gs = torch.empty(1, device=dev, dtype=torch.float32)   # g / n_live: the factor of dl; |gs| bounds it (the weight is not in dl)
+        gslot = torch.empty(1, device=dev, dtype=torch.int32)
+        call("care_head_reward_gscale", ptr(g32), ptr(totals), ptr(gs), gslot.data_ptr(), tag="head_reward_gscale")
+        ksd, ksv = criterion._ceil64(d), criterion._ceil64(V)
+        dh_live = torch.empty(R, d, device=dev, dtype=torch.float32) if need_dh else None
+        wh = wh_slot = None
+        if need_dw:   # w (.) h_live: the B operand of dW = dl^T (w (.) h), pieces from a |max| of its own
+            wh = torch.empty(R, d, device=dev, dtype=torch.float32)
+            call("care_rows_scale", ptr(h_live), d, ptr(cst[3]), ptr(wh), d, R, d, tag="rows_scale")
+            wh_slot = _absmax_slot(wh)
+        plan = [(a, b, _x3_slabs(V, d, b - a)) for a, b in criterion.head_chunks(R)]
+        terms = sum(s for _, _, s in plan)
+        dw_terms, at = None, 0
+        for a, b, slabs in plan:   # _HeadLoss.backward's buffers and their order: one of the size of W's pieces or the chunk's at a time
+            n = b - a
+            w3 = torch.empty(V, 3 * ksd, device=dev, dtype=torch.float16)
+            call("care_split_pieces", ptr(Wc), Wc.stride(0), V, d, 0, 1, ksd, ptr(w3), 3, w_slot.data_ptr())
+            dl2 = torch.empty(n, 2 * ksv, device=dev, dtype=torch.float16)
+            call("care_gemm_tile_split3_head_grad", ptr(a2[a:]), ptr(w3), h_slot.data_ptr(), w_slot.data_ptr(), ptr(idx[2][a:]),
+                 ptr(cst[0][a:]), ptr(cst[1][a:]), ptr(gs), gslot.data_ptr(), 0.0, ptr(dl2), n, V, ksd)
+            del w3
+            if need_dh:   # dl W: W^T as the [d, V] operand, pieces with the forward's |max| of W; the weight follows below
+                wt3 = torch.empty(d, 3 * ksv, device=dev, dtype=torch.float16)
+                call("care_split_pieces", ptr(Wc), Wc.stride(0), d, V, 1, 1, ksv, ptr(wt3), 3, w_slot.data_ptr())
+                call("care_gemm_tile_split3_scaled", ptr(dl2), ptr(wt3), None, ptr(dh_live[a:]), d, n, d, ksv, gslot.data_ptr(),
+                     w_slot.data_ptr(), 1)
+                del wt3
+            if need_dw:   # dW = dl^T (w (.) h): the reduction runs over the chunk's rows, in slabs when the output has few tiles
+                ksr = criterion._ceil64((n + slabs - 1) // slabs)
+                dlt = torch.empty(slabs * V, 2 * ksr, device=dev, dtype=torch.float16)
+                call("care_pieces_transpose", ptr(dl2), n, V, ksv, slabs, ksr, ptr(dlt))
+                del dl2
+                if dw_terms is None:
+                    dw_terms = torch.empty(terms * V, d, device=dev, dtype=torch.float32)
+                ht3 = torch.empty(slabs * d, 3 * ksr, device=dev, dtype=torch.float16)
+                call("care_split_pieces", ptr(wh[a:]), d, d, n, 1, slabs, ksr, ptr(ht3), 3, wh_slot.data_ptr())
+                call("care_gemm_tile_split3_scaled", ptr(dlt), ptr(ht3), None, ptr(dw_terms[at * V:]), d, V, d, ksr, gslot.data_ptr(),
+                     wh_slot.data_ptr(), slabs)
+                at += slabs
+                del dlt, ht3
+        dW = None
+        if need_dw:   # slabs and chunks added in order: one grouping, the same bits every time
+            dW = dw_terms if terms == 1 else _strided_sum(dw_terms, V, terms, 1, V)
+        dhid = None
+        if need_dh:   # dh = w (.) (dl W), in place, then to its rows: the dead rows stay the zeros of the fill
+            call("care_rows_scale", ptr(dh_live), d, ptr(cst[3]), ptr(dh_live), d, R, d, tag="rows_scale")
+            dhid = zeros(rows_h, d)
+            call("care_scatter_rows", ptr(dh_live), d * 4, ptr(dhid), d * 4, ptr(idx[0]), R, d * 4)
+        return dhid, dW, None, None, None, None
+
+
+def self_critical_head_loss(hidden, weight, labels, advantages, acc: Optional[torch.Tensor] = None, return_aux: bool = False,
+                            live: Optional[int] = None):
+    """`self_critical_loss` with the vocabulary head inside: the loss of the logits hidden . weight^T that are
+    never written, as a 0-dim fp32 device tensor under autograd with gradients to `hidden` and `weight`.
+
+    hidden fp32 [N, t, d] (or [N, t + 1, d]: the last position is dead), weight [V, d] - what a training forward under
+    set_fused_head(True) hands over as a DeferredLogits -, labels [N, t] with PAD (or anything outside [1, V)) = a dead
+    position, advantages [N].  Head, loss and backward run over the live positions only, as split fp16 products (the `fp16x3`
+    form) in chunks of criterion.HEAD_CHUNK_ROWS rows; dead rows of the gradient of `hidden` are exact zeros whatever the dead
+    rows of `hidden` hold.  acc / return_aux: as in `self_critical_loss`.  live: the number of live label positions if the
+    caller has it on the host; None: it is read back from the device - 4 bytes, the call's one synchronisation."""
+    for what, t in (("hidden", hidden), ("weight", weight), ("labels", labels), ("advantages", advantages)):
+        need_device(t, what, "the self-critical loss")
+    if hidden.dtype != torch.float32:
+        raise TypeError("`hidden` must be fp32, got {}".format(hidden.dtype))
+    if weight.dtype != torch.float32:
+        raise TypeError("`weight` must be fp32, got {}".format(weight.dtype))
+    if hidden.dim() != 3 or weight.dim() != 2 or hidden.shape[2] != weight.shape[1]:
+        raise ValueError("hidden [N, t (+ 1), d] and weight [V, d] expected, got {} and {}".format(tuple(hidden.shape), tuple(weight.shape)))
+    if labels.dim() != 2 or labels.shape[0] != hidden.shape[0] or hidden.shape[1] not in (labels.shape[1], labels.shape[1] + 1):
+        raise ValueError("hidden [N, t (+ 1), d] and labels [N, t] expected, got {} and {}".format(tuple(hidden.shape), tuple(labels.shape)))
+    if advantages.numel() != hidden.shape[0]:
+        raise ValueError("`advantages` holds {} entries for N = {} captions".format(advantages.numel(), hidden.shape[0]))
+    if hidden.numel() == 0 or labels.numel() == 0 or weight.numel() == 0:
+        raise ValueError("the loss of empty hidden states {} / weight {} is undefined".format(tuple(hidden.shape), tuple(weight.shape)))
+    if weight.device != hidden.device or labels.device != hidden.device or advantages.device != hidden.device:
+        raise RuntimeError("hidden states are on `{}`, weight on `{}`, labels on `{}`, advantages on `{}`".format(
+            hidden.device, weight.device, labels.device, advantages.device))
+    if acc is not None and (acc.dtype != torch.float64 or acc.numel() < 2 or acc.device != hidden.device):
+        raise ValueError("`acc` must hold 2 float64 entries on {}".format(hidden.device))
+    if live is not None and not 0 <= int(live) <= labels.numel():
+        raise ValueError("`live` = {} for {} label positions".format(live, labels.numel()))
+    labels32 = labels.to(torch.int32).contiguous()
+    adv = advantages.detach().to(torch.float32).reshape(-1).contiguous()
+    N, tl, d = hidden.shape
+    with torch.cuda.device(hidden.device):
+        loss, seq_logp, totals = _HeadRewardLoss.apply(hidden.reshape(N * tl, d), weight, labels32, adv, acc, live)
     return (loss, seq_logp, totals) if return_aux else loss

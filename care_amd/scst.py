@@ -11,13 +11,19 @@ log-likelihood (care_amd.reward.self_critical_loss).  The sampled tokens, their 
 number of live label positions stay on the device from the first launch to the optimiser step: the host reads nothing of
 them, `last` holds device scalars, and reading one is the caller's synchronisation.
 
-What it does not do: ensembles, the fused head (the loss is taken over the [N, t, V] logits), a cross-entropy term mixed
-into the step, and the exchange of gradients between devices.
+`fused_head=True` runs the teacher-forced pass with the vocabulary head inside the loss
+(care_amd.reward.self_critical_head_loss): head, loss and backward over the live label positions only, the
+[N, t, V] logits and their gradient never in memory.  The unfused step stays free of result reads; the fused one has a single
+one - the number of live label positions, 4 bytes, counted on the device and copied to pinned memory without blocking
+BEFORE the teacher-forced forward is enqueued, and waited for only when the loss is reached: the read overlaps the forward.
+
+What it does not do: ensembles, a cross-entropy term mixed into the step, and the exchange of gradients between devices.
 """
 import torch
 
 from .constants import PAD
-from .reward import CiderBank, reward_advantage, self_critical_loss
+from .criterion import DeferredLogits
+from .reward import CiderBank, reward_advantage, self_critical_head_loss, self_critical_loss
 
 __all__ = ["SelfCriticalStep", "sample_to_labels"]
 
@@ -40,10 +46,16 @@ class SelfCriticalStep(object):
     care_amd.optim.configure_optimizers unless given, as InterplayStep does).
 
     baseline "greedy": advantage = reward - reward of the clip's greedy caption (one more decode per step);
-    baseline "mean":   advantage = reward - mean reward of the clip's other n_samples - 1 samples."""
+    baseline "mean":   advantage = reward - mean reward of the clip's other n_samples - 1 samples.
+
+    fused_head False (the default): the loss over the [N, t, V] logits; a captioner with set_fused_head(True) is refused.
+    fused_head True: the captioner is accepted whatever its own flag says; the step turns the module's fused head on for the
+    teacher-forced pass only (the caller's value comes back in a `finally`) and takes the loss with the head inside -
+    `last` then holds `seq_logp` (each caption's sum of log-probabilities) and no `logits`.  The unfused step reads no
+    result on the host; the fused one reads the live count - 4 bytes, once, overlapped with the forward."""
 
     def __init__(self, opt, captioner, bank, n_samples=5, baseline="greedy", temperature=1.0, top_k=0, top_p=1.0, optimizer=None,
-                 scheduler=None, with_eos=None):
+                 scheduler=None, with_eos=None, fused_head=False):
         from .engine_sample import check_sample_args
         from .optim import configure_optimizers
 
@@ -59,7 +71,9 @@ class SelfCriticalStep(object):
         if with_eos is not None and bool(with_eos) != bank.with_eos:
             raise ValueError("`with_eos` = {} but the bank was built with with_eos = {}: candidates and references must "
                              "treat EOS alike".format(bool(with_eos), bank.with_eos))
-        self._refuse_fused_head(captioner)
+        self.fused_head = bool(fused_head)
+        if not self.fused_head:
+            self._refuse_fused_head(captioner)
         self.opt, self.captioner, self.bank = opt, captioner, bank
         self.n_samples, self.baseline = n_samples, baseline
         self.temperature, self.top_k, self.top_p = temperature, top_k, top_p
@@ -86,12 +100,13 @@ class SelfCriticalStep(object):
 
     def training_step(self, batch, seed=None, current_epoch=0):
         """Returns the loss; `last` holds loss, mean_reward and mean_baseline as detached device scalars, and the device tensors
-        the step worked on (tokens, length, reward, advantages, input_ids, labels, logits; greedy_tokens / greedy_length
-        with the greedy baseline).  seed None: one from torch's generator."""
+        the step worked on (tokens, length, reward, advantages, input_ids, labels, logits - with fused_head: seq_logp
+        instead of logits -; greedy_tokens / greedy_length with the greedy baseline).  seed None: one from torch's generator."""
         if "video_ids" not in batch:
             raise KeyError("the batch has no `video_ids`: the reward is taken against each clip's own references")
         model, n = self.captioner, self.n_samples
-        self._refuse_fused_head(model)
+        if not self.fused_head:
+            self._refuse_fused_head(model)
         feats = list(batch["feats"])
         if any(f.device.type != "cuda" for f in feats):
             raise RuntimeError("the features are on the CPU: self-critical training runs on the MI355X (no CPU fallback)")
@@ -127,8 +142,12 @@ class SelfCriticalStep(object):
         tf_batch["feats"] = [f.repeat_interleave(n, dim=0) for f in feats]
         tf_batch["input_ids"], tf_batch["labels"] = input_ids, labels
         try:
-            results = model(tf_batch, current_epoch=current_epoch)
-            loss = self_critical_loss(results["logits"], labels, adv.view(-1))
+            if self.fused_head:
+                loss, out = self._fused_loss(model, tf_batch, labels, adv, current_epoch)
+            else:
+                results = model(tf_batch, current_epoch=current_epoch)
+                loss = self_critical_loss(results["logits"], labels, adv.view(-1))
+                out = {"logits": results["logits"].detach()}
             self.optimizer.zero_grad()
             loss.backward()
             self.optimizer.step()
@@ -136,8 +155,34 @@ class SelfCriticalStep(object):
             model.train(was_training)
         self.last = {"loss": loss.detach(), "mean_reward": stats[0], "mean_baseline": stats[1],
                      "tokens": fed, "length": length, "score": score, "reward": reward, "advantages": adv,
-                     "input_ids": input_ids, "labels": labels, "logits": results["logits"].detach(), **greedy}
+                     "input_ids": input_ids, "labels": labels, **out, **greedy}
         return loss
+
+    def _fused_loss(self, model, tf_batch, labels, adv, current_epoch):
+        """The teacher-forced pass with the module's fused head on and the loss with the head inside.  The live count leaves
+        for pinned memory before the forward is enqueued and is waited for behind it: the step's one result read."""
+        V = int(self.opt["vocab_size"])
+        count = ((labels > 0) & (labels < V)).sum().to(torch.int32)
+        host = torch.empty((), dtype=torch.int32, pin_memory=True)
+        host.copy_(count, non_blocking=True)
+        arrived = torch.cuda.Event()
+        arrived.record(torch.cuda.current_stream(labels.device))
+        was_fused = bool(getattr(model, "fused_head", False))
+        model.set_fused_head(True)
+        try:
+            results = model(tf_batch, current_epoch=current_epoch)
+        finally:
+            model.set_fused_head(was_fused)
+        deferred = results["logits"]
+        if not isinstance(deferred, DeferredLogits):
+            raise RuntimeError("the training forward under set_fused_head(True) returned {} under `logits`, not a "
+                               "DeferredLogits".format(type(deferred).__name__))
+        if deferred.weight.shape[0] != V:
+            raise ValueError("opt['vocab_size'] = {} but the head has {} rows".format(V, deferred.weight.shape[0]))
+        arrived.synchronize()
+        loss, seq_logp, _ = self_critical_head_loss(deferred.hidden, deferred.weight, labels, adv.view(-1), return_aux=True,
+                                                    live=int(host))
+        return loss, {"seq_logp": seq_logp}
 
     def training_epoch_end(self) -> None:
         """The scheduler is stepped by hand, as InterplayStep does (manual optimisation)."""

@@ -755,6 +755,42 @@ int care_gemm_tile_split3_head_grad(const void* A2, const void* W3, const void* 
 int care_pieces_transpose(const void* src, int R, int V, int ks_v, int slabs, int ks_r, void* out, void* stream);
 
 /*
+ * The training head fused with the self-critical loss (models/Head.py:26-32: logits = hidden tgt_word_prj^T; the loss of
+ * care_reward_loss_fwd - misc/Crit/crit_lang.py:57-60's log_softmax at the label, weighted per caption, no label smoothing;
+ * care_amd/reward.py, _HeadRewardLoss):
+ *     loss = -(1 / n_live) sum over live rows i of w[i] logp[i],   w[i] = adv[caption of row i].
+ * The forward is care_head_live_rows, care_gather_rows, care_split_pieces and care_gemm_tile_split3_head_stats as they are.  The
+ * gradient of the logits of live row i is (g w[i] / n_live) (softmax - onehot): care_gemm_tile_split3_head_grad with eps = 0 and
+ * the device scalar g / n_live writes dl WITHOUT the weight, which is linear and goes onto the d-wide sides:
+ *     dh[i] = w[i] (dl[i] W),   dW = dl^T (w (.) h_live)   (Head.py:26-32 backward).
+ *
+ * care_head_reward_finish (crit_lang.py:57-60): merges the parts (pmax, psum, plab of care_gemm_tile_split3_head_stats,
+ *   arrays [R, parts], parts = care_argmax_parts_tile(V)) of live row i < R into rmax_c[i] = max x, lsum_c[i] =
+ *   log sum exp(x - max), logp_c[i] = (x[y] - rmax) - lsum - care_head_loss_finish's bits - and writes the row's weight
+ *   w_c[i] = adv[idx_l[i] / t] (idx_l: the label positions of care_head_live_rows, t positions per caption).  One wave per
+ *   row, a fixed order.  R == 0 launches nothing.
+ * care_head_reward_reduce: the outputs of care_reward_loss_fwd, with the same meaning, from the compact rows: totals[0] =
+ *   sum w_c logp_c (a weight of exactly 0 adds nothing), totals[1] = R, *loss (DEVICE float) = -(totals[0] / R), 0 for R == 0;
+ *   seq_logp (optional) [n_seq]: each caption's sum of logp over its live rows, 0 without one; acc (optional): += (loss, R).
+ *   One workgroup, every sum in double and in one order, no floating-point atomics: two calls give the same bits.
+ * care_head_reward_gscale: *gs = (float)(*g / totals[1]) (0 for totals[1] == 0), *slot = the bit pattern of |*gs| (one
+ *   thread) - care_head_grad_scale's role: |dl| <= |gs| because the weight is not in dl.
+ * care_rows_scale: dst[i, :] = w[i] src[i, :], fp32 [rows, cols] with row strides ld_src, ld_dst >= cols (elements); dst may
+ *   be src.  16-byte accesses when cols, both strides and both pointers allow them.  rows == 0 launches nothing.
+ * All four: a NULL pointer (but the optional ones) or a negative size -> CARE_EINVAL; totals / acc not 8-byte aligned ->
+ *   CARE_EALIGN; parts != care_argmax_parts_tile(V), R > n_seq t or a stride below cols -> CARE_ESHAPE; all before anything is
+ *   launched.
+ */
+int care_head_reward_finish(const float* pmax, const float* psum, const float* plab, int parts, const int32_t* idx_l,
+                            const float* adv, int t, int V, int R, float* rmax_c, float* lsum_c, float* logp_c, float* w_c,
+                            void* stream);
+int care_head_reward_reduce(const float* logp_c, const float* w_c, const int32_t* idx_l, int R, int t, int n_seq, double* totals,
+                            float* loss, float* seq_logp, double* acc, void* stream);
+int care_head_reward_gscale(const float* g, const double* totals, float* gs, void* slot, void* stream);
+int care_rows_scale(const float* src, int64_t ld_src, const float* w, float* dst, int64_t ld_dst, int rows, int cols,
+                    void* stream);
+
+/*
  * The optimiser step (models/Wrapper.py:316-386: configure_optimizers builds torch.optim.Adam; train.py:128 / opts.py:145:
  * Lightning's gradient_clip_val runs clip_grad_norm_ before it; misc/utils.py:282-304: the weight-decay groups; care_amd/optim.py).
  * One sweep for the norm of all gradients and one for the update of all parameters, whatever the number of tensors.  fp32 in

@@ -1,6 +1,6 @@
 """Self-critical training, timed (one JSON line):
 
-    python tools/scst_bench.py [--videos 6513] [--refs 20] [--windows 5] [--window-s 0.3] [--no-step]
+    python tools/scst_bench.py [--videos 6513] [--refs 20] [--windows 5] [--window-s 0.3] [--no-step] [--fused-head]
 
 1. THE REWARD ALONE: CiderBank.score (care_cider_score) at 128 and 640 candidates of 30 tokens against a synthetic
    MSRVTT-shaped corpus (6513 videos x 20 references of 5 .. 14 words + EOS, V = 10547, words drawn from a Zipf-like law so that
@@ -13,6 +13,11 @@
    gather, weighted mean) and against care_lang_loss_fwd / _bwd (eps = 0) on the same logits and labels.
 3. THE WHOLE STEP at 128 clips x 5 samples (msrvtt_care, greedy baseline): SelfCriticalStep.training_step, the same step with
    the reward computed on the host, and the plain cross-entropy step of tools/train_prof.py at 640 sequences.
+
+With --fused-head (and nothing else measured): the loss WITH the head, forward + backward, on hidden states [640, 29, 512] -
+care_amd.self_critical_head_loss against `_Linear` + self_critical_loss - and SelfCriticalStep(fused_head=True) against the
+unfused step at 128 clips x 5; each with every position live (the synthetic model never draws EOS) and with the captions cut to
+5 .. 14 tokens (about a quarter live), with the peak memory each variant allocates above its starting level.
 
 tools/loss_bench.py's method: device events around a window of calls; every variant warmed up first; the variants ALTERNATE
 window by window in one process; medians of >= 5 windows of >= 0.3 s each, with min and max.
@@ -184,6 +189,90 @@ def whole_step(bank, corpus, clips, n, dev, n_windows, window_s):
                 mean_reward=float(hip.last["mean_reward"]), **{k: summary(v) for k, v in ts.items()})
 
 
+def cut_lengths(rows, seed, dev):
+    """int32 [rows]: caption lengths of 5 .. 14 tokens (the corpus' own law) - about a quarter of 29 positions live."""
+    return torch.from_numpy(np.random.RandomState(seed).randint(5, 15, size=rows).astype(np.int32)).to(dev)
+
+
+def peak_rise(fn):
+    """Bytes one call of `fn` allocates above its starting level at its peak."""
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
+    base = torch.cuda.memory_allocated()
+    fn()
+    torch.cuda.synchronize()
+    return torch.cuda.max_memory_allocated() - base
+
+
+def head_loss_alone(seqs, d, dev, n_windows, window_s, quarter):
+    """The loss with the head, forward + backward, on hidden states [seqs, 29, d]: self_critical_head_loss (the live count given,
+    as SelfCriticalStep gives it) against `_Linear` + self_critical_loss on the same hidden states.  quarter: captions of 5 .. 14
+    tokens; else every position live (what the synthetic model of the whole step samples: it never draws EOS)."""
+    from care_amd import self_critical_head_loss
+    from care_amd.training import _Linear
+
+    gen = torch.Generator(device=dev).manual_seed(seqs + int(quarter))
+    hidden = torch.randn(seqs, T, d, generator=gen, device=dev).requires_grad_(True)
+    W = (torch.randn(V, d, generator=gen, device=dev) * (2.0 / math.sqrt(d))).requires_grad_(True)
+    labels = torch.randint(6, V, (seqs, T), generator=gen, device=dev)
+    if quarter:
+        labels = torch.where(torch.arange(T, device=dev).view(1, T) < cut_lengths(seqs, 3, dev).view(-1, 1), labels, torch.zeros_like(labels))
+    live = int((labels != PAD).sum())
+    adv = torch.randn(seqs, generator=gen, device=dev)
+
+    def fused():
+        hidden.grad = W.grad = None
+        self_critical_head_loss(hidden, W, labels, adv, live=live).backward()
+
+    def unfused():
+        hidden.grad = W.grad = None
+        self_critical_loss(_Linear.apply(hidden.view(seqs * T, d), W, None).view(seqs, T, V), labels, adv).backward()
+
+    fused()
+    gh, gw, lf = hidden.grad.clone(), W.grad.clone(), float(self_critical_head_loss(hidden, W, labels, adv, live=live).detach())
+    unfused()
+    diff_h = float((gh - hidden.grad).abs().max() / hidden.grad.abs().max())
+    diff_w = float((gw - W.grad).abs().max() / W.grad.abs().max())
+    lu = float(self_critical_loss(_Linear.apply(hidden.view(seqs * T, d), W, None).view(seqs, T, V), labels, adv).detach())
+    del gh, gw
+    peaks = {"fused": peak_rise(fused), "unfused": peak_rise(unfused)}
+    ts = windows({"fused": fused, "unfused": unfused}, n_windows, window_s)
+    med = {k: statistics.median(v) for k, v in ts.items()}
+    return dict(sequences=seqs, positions=seqs * T, live_rows=live, live_share=round(live / (seqs * T), 3), d=d,
+                **{k: summary(v) for k, v in ts.items()}, unfused_over_fused=round(med["unfused"] / med["fused"], 3),
+                peak_rise_mb={k: round(v / 2 ** 20, 1) for k, v in peaks.items()}, one_logits_tensor_mb=round(seqs * T * V * 4 / 2 ** 20, 1),
+                loss_fused=lf, loss_unfused=lu, max_rel_dhidden_difference=diff_h, max_rel_dw_difference=diff_w)
+
+
+def whole_step_fused(bank, clips, n, dev, n_windows, window_s, quarter):
+    """SelfCriticalStep with fused_head=True against the same step without, alternated.  quarter: the sampled captions are cut
+    to 5 .. 14 tokens behind the decode (the synthetic model never draws EOS: all 29 positions of every sample are live)."""
+    from care_amd import scst
+
+    opt = make_opt("msrvtt_care", label_smoothing=EPS, gradient_clip_val=5.0)
+    gen = torch.Generator(device=dev).manual_seed(5)
+    feats = [torch.randn(s, generator=gen, device=dev) for s in feat_shapes(opt, clips)]
+    batch = {"feats": feats, "video_ids": np.random.RandomState(2).randint(0, bank.n_videos, size=clips).tolist()}
+    steps = {"fused": SelfCriticalStep(opt, _model(opt, 0, dev), bank, n_samples=n, baseline="greedy", fused_head=True),
+             "unfused": SelfCriticalStep(opt, _model(opt, 0, dev), bank, n_samples=n, baseline="greedy")}
+    plain, cut = scst.sample_to_labels, cut_lengths(clips * n, 4, dev)
+    if quarter:
+        scst.sample_to_labels = lambda fed, length, t: plain(fed, torch.minimum(length, cut), t)
+    try:
+        peaks = {}
+        for k, s in steps.items():
+            s.training_step(batch)      # (the first step builds the optimiser's state)
+            peaks[k] = peak_rise(lambda: s.training_step(batch))
+        ts = windows({k: (lambda s=s: s.training_step(batch)) for k, s in steps.items()}, n_windows, window_s)
+    finally:
+        scst.sample_to_labels = plain
+    med = {k: statistics.median(v) for k, v in ts.items()}
+    live = int((steps["fused"].last["labels"] != PAD).sum())
+    return dict(clips=clips, n_samples=n, sequences=clips * n, live_positions=live, live_share=round(live / (clips * n * T), 3),
+                **{k: summary(v) for k, v in ts.items()}, unfused_over_fused=round(med["unfused"] / med["fused"], 3),
+                peak_rise_mb={k: round(v / 2 ** 20, 1) for k, v in peaks.items()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--videos", type=int, default=6513)
@@ -191,6 +280,8 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--window-s", type=float, default=0.3)
     ap.add_argument("--no-step", action="store_true", help="skip the whole training step")
+    ap.add_argument("--fused-head", action="store_true", help="the fused-head variants of the loss rows and of the whole-step row, "
+                    "each against the unfused path, with every position live and with about a quarter live - and nothing else")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("scst_bench.py measures on the MI355X: no GPU, no numbers")
@@ -201,6 +292,13 @@ def main():
     t0 = time.perf_counter()
     bank = CiderBank(refs, V, with_eos=True, device=dev)
     build_s = time.perf_counter() - t0
+    if a.fused_head:
+        res = dict(tool="scst_bench --fused-head", vocab=V,
+                   head_loss=[head_loss_alone(640, 512, dev, a.windows, a.window_s, quarter) for quarter in (False, True)])
+        if not a.no_step:
+            res["whole_step"] = [whole_step_fused(bank, 128, 5, dev, a.windows, a.window_s, quarter) for quarter in (False, True)]
+        print(json.dumps(res))
+        return
     corpus = cider_reference.Corpus(refs, with_eos=True)
     res = dict(tool="scst_bench", corpus=dict(videos=a.videos, refs_per_video=a.refs, vocab=V, unique_ngrams=int(bank.host["corpus_keys"].size),
                                               reference_keys=int(bank.host["ref_keys"].size), bank_build_s=round(build_s, 2)),
